@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py — points/sec through the KNN + group + local-aggregation + CBL block on S3DIS-shaped synthetic scenes.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--points 40960] [--channels 64] [--k 16] [--forward-only]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--points 40960] [--channels 64] [--k 16] [--forward-only] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets the step up, runs W warm-up steps, times exactly K steps in one region and prints the headline (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, ...).  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (same arguments,
+same inputs: two builds can be compared output for output).  `--full` adds the median of three timed regions as the headline and everything the
+line carries beside it (below).
 
 One "step" = one pass of the hot path (contrastboundary_amd/hotpath.py: search, gather, KPConv, CBL head forward + backward and — BASELINE
 config C2 "forward/backward" — the block's backward legs) over one scene whose inputs are already resident in HBM.  Scenes are independent,
@@ -11,7 +16,7 @@ re-executes this file under torch.distributed.run with N ranks (one per device; 
 number of ranks that joined the process group.  Every timed step is the same thing: the step's hipGraphs replayed, consecutive steps
 software-pipelined (hotpath.Pipeline: the search of step i+1 beside the gather / KPConv / backward kernels of step i; `--no-pipeline`: one
 graph per step, every step on its own).  The timed region is bracketed by barrier + synchronize (the whole device) and the MAX over ranks is
-used.  Rank 0 prints ONE JSON line with the driver's fields plus
+used.  Rank 0 prints ONE JSON line with the driver's fields, and with `--full`
   `roofline`      the HBM-bound neighbour gather: algorithmic bytes / HIP-event duration of its launch alone (back-to-back launches behind a
                   filler kernel, events on the launch stream), with the K4 gather and the KPConv kernel beside it, the in-order per-stage
                   times, PMC traffic from profiles/ if it belongs to this kernel set;
@@ -67,12 +72,19 @@ def parse(argv=None):
     ap.add_argument("--no-extra", action="store_true", help="headline only: no forward_only / stage / all-reduce legs (profiling runs)")
     ap.add_argument("--no-gather-200k", action="store_true", help="skip the HBM-certain gather measurement (N = 200 000: 857 MB per launch) of the roofline object")
     ap.add_argument("--no-legs", action="store_true",
-                    help="default line only: skip the `pt_block` (config C4) and `convnet` (configs C5 / C3 per scene) legs the 1-GPU default run appends")
+                    help="default line only: skip the `pt_block` (config C4) and `convnet` (configs C5 / C3 per scene) legs the 1-GPU --full run appends")
     ap.add_argument("--allreduce-floats", type=int, default=GRAD_ALLREDUCE_FLOATS)
     ap.add_argument("--allreduce-single", action="store_true",
                     help="tests: run the gradient all-reduce leg over a ONE-rank RCCL group (exercises the RCCL path on a 1-GPU box; not a scaling number)")
     ap.add_argument("--host-dry-run", action="store_true",
                     help="CPU-only run of the launcher / process-group / timing / all-reduce logic over gloo (tests; not a measurement)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: three timed regions (median), roofline and per-stage times, forward_only / no_pipeline / all-reduce "
+                         "steps, cpu_baseline and the legs of the other workloads.  Without it a run sets up, warms up, times exactly --steps steps once "
+                         "and prints the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64; integer outputs as float64, "
+                         "the order-free K=36 rows sorted; at most 60 MB: past that, the largest per-point outputs keep one seeded sample of rows, DIR/rows.npy)")
     args = ap.parse_args(argv)
     if args.points is None:
         args.points = 200000 if args.workload == "convnet" else 40960
@@ -158,6 +170,59 @@ class GradAllReduce:
         self.pending = []
 
 
+def timed_headline(step, args, sync, D):
+    """the headline's clock: exactly --steps timed steps in one region (timed_region); --full keeps three regions and reports the median one
+    (timed_median).  -> (elapsed seconds, [ms per step of every region])"""
+    if args.full:
+        return timed_median(step, args.steps, args.warmup, sync, D)
+    e = timed_region(step, args.steps, args.warmup, sync, D)
+    return e, [round(e / args.steps * 1e3, 5)]
+
+
+REGIONS_NOTE = {True: "three regions of --steps steps each, barrier + synchronize around every one; value / ms_per_step = the median region",
+                False: "one region of exactly --steps steps, barrier + synchronize around it (--full: three regions, the median one)"}
+
+
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_CAP_BYTES = 60 * 10 ** 6
+DUMP_KEYS = ("idx", "dist2", "grouped", "kpconv", "pt_out", "cbl_idx", "cbl_loss", "cbl_grad", "grad_feat_group", "grad_feat_kpconv",
+             "grad_kernel_weights", "grad_feat_pt", "grad_params_pt")
+
+
+def dump_outputs(state, n, out_dir, seed=0):
+    """what one step of the block hands its caller (hotpath.stages / stages_pt state) as out_dir/<name>.npy: float outputs as float32, integer ones
+    as float64 (exact), the K=36 rows of the order-free CBL search sorted (the set is the result, not its order).  If everything does not fit in
+    DUMP_CAP_BYTES, the largest outputs whose first axis is the scene's n points keep one seeded sample of rows (out_dir/rows.npy), shared by
+    all of them, and the others are written whole.  -> {name: shape}"""
+    arrays = {}
+    for key in DUMP_KEYS:
+        v = state.get(key)
+        if v is None:
+            continue
+        for i, t in enumerate(v) if isinstance(v, (tuple, list)) else [(None, v)]:
+            a = t.detach().cpu().numpy()
+            if key == "cbl_idx":
+                a = np.sort(a, axis=1)
+            arrays[key if i is None else "%s_%d" % (key, i)] = a.astype(np.float32 if np.issubdtype(a.dtype, np.floating) else np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_CAP_BYTES:
+        per_point = sorted((nm for nm, a in arrays.items() if a.ndim and a.shape[0] == n), key=lambda nm: arrays[nm].nbytes)
+        sampled, whole = [], total
+        while per_point and whole > DUMP_CAP_BYTES * 3 // 4:      # a quarter of the budget at least for the sampled rows
+            sampled.append(per_point.pop())
+            whole -= arrays[sampled[-1]].nbytes
+        m = min(n, (DUMP_CAP_BYTES - whole) // (8 + sum(arrays[nm].nbytes // n for nm in sampled)))
+        rows = np.sort(np.random.default_rng(seed).choice(n, m, replace=False))
+        for nm in sampled:
+            arrays[nm] = arrays[nm][rows]
+        arrays["rows"] = rows.astype(np.float64)
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_CAP_BYTES
+    os.makedirs(out_dir, exist_ok=True)
+    for nm, a in arrays.items():
+        np.save(os.path.join(out_dir, nm + ".npy"), a)
+    return {nm: list(a.shape) for nm, a in arrays.items()}
+
+
 # ------------------------------------------------------------------------------------------------ host dry run (gloo, CPU): tests only
 def host_dry_run(args, D, world, rank):
     """the N > 1 logic of this file without a GPU: rendezvous, world-size check, barrier-bracketed timing, max over ranks, the all-reduce
@@ -229,6 +294,12 @@ class Step:
     @property
     def state(self):
         return self.states[-1]
+
+    def last_state(self):
+        """the outputs of the step issued last (the pipeline's steps rotate through its slots)"""
+        if self.pipe is not None:
+            return self.pipe.states[(self.pipe.count - 1) % self.pipe.SLOTS]
+        return self.states[0]
 
     def eager(self, events=None):
         self.sched.run(self.states[0], events)
@@ -577,10 +648,10 @@ def run_gpu(args, D, world, rank, local):
     step, pipe_check = checked_pipeline_step(scene, k, backward, args, overlap=not args.no_overlap, pipeline=pipeline)
     sync = torch.cuda.synchronize
 
-    elapsed, regions = timed_median(step, args.steps, args.warmup, sync, D)
+    elapsed, regions = timed_headline(step, args, sync, D)
     spread = rank_spread(D)
     out = {
-        "ranks": spread, "pipeline_check": pipe_check, "timed_regions_ms_per_step": regions, "timed_regions_note": "three regions of --steps steps each, barrier + synchronize around every one; value / ms_per_step = the median region",
+        "ranks": spread, "pipeline_check": pipe_check, "timed_regions_ms_per_step": regions, "timed_regions_note": REGIONS_NOTE[args.full],
         "metric": "points/sec through KNN+group+KPConv+CBL block, S3DIS N=40960 K=16",
         "value": n * args.steps * world / elapsed, "unit": "points/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": elapsed / args.steps * 1e3, "host_issue_ms_per_step": timed_region.issue_s / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -598,7 +669,9 @@ def run_gpu(args, D, world, rank, local):
                                 "replay: mostly small latency-bound launches) runs beside the forward kernels of step i and the backward kernels of step i-1"
                                 if step.pipe is not None else "")},
     }
-    if args.no_extra:
+    if args.dump_outputs and rank == 0:
+        out["dumped_outputs"] = dump_outputs(step.last_state(), n, args.dump_outputs)
+    if args.no_extra or not args.full:
         if rank == 0:
             print(json.dumps(out), flush=True)
         return finish(world)
@@ -721,14 +794,14 @@ def run_gpu(args, D, world, rank, local):
 
 # ------------------------------------------------------------------------------------------------ C4 / C5 legs of the default line
 def workload_legs(args):
-    """The driver only ever runs the default command line, so the 1-GPU default run also measures BASELINE's other two single-GPU configurations —
+    """The 1-GPU `--full` run of the default command line also measures BASELINE's other two single-GPU configurations —
     C4 (`--block pt`: the Point Transformer's vector-attention block) and C5 / C3-per-scene (`--workload convnet`) — each in a process of its own
     (own graphs, caches, scene) with the same timing contract, and appends a compact object per leg: {metric, value, ms_per_step, steps, roofline ...}.
     A leg that fails is reported as {"error": ...} and does not take the headline down."""
     import subprocess
 
     def leg(extra, pick):
-        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--no-cpu-baseline", "--no-legs"] + extra
+        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--full", "--no-cpu-baseline", "--no-legs"] + extra
         env = dict(os.environ)
         for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
             env.pop(k, None)
@@ -741,7 +814,7 @@ def workload_legs(args):
             o = {k: d[k] for k in ("metric", "value", "unit", "ms_per_step", "steps", "warmup", "host_issue_ms_per_step", "dtype", "timed_regions_ms_per_step") if k in d}
             o["workload"] = d.get("config", {}).get("workload")
             o["issue"] = d.get("config", {}).get("issue")
-            o["command"] = "python bench.py " + " ".join(extra)
+            o["command"] = "python bench.py --full " + " ".join(extra)
             o.update(pick(d))
             return o
         except Exception as e:                                       # noqa: BLE001 — a leg must not take the headline down
@@ -928,7 +1001,7 @@ def run_convnet(args, D, world, rank, local):
                       "parallelism": "scene-per-GPU replicas x%d (no data-path collective)" % world,
                       "issue": ((pipelined["issue"] if pipelined is not None and pipelined["ms_per_step"] <= in_order["ms_per_step"] else in_order["issue"])
                                 + "; data-dependent layer sizes: one host wait per grid subsampling, like the TF op's dynamic shape")}}
-    if args.no_extra:
+    if args.no_extra or not args.full:
         if rank == 0:
             print(json.dumps(out), flush=True)
         return finish(world)
@@ -1147,8 +1220,8 @@ def run_pt(args, D, world, rank, local):
     pipeline = not (args.no_pipeline or args.no_overlap or args.no_nested or args.no_graph)
     step, pipe_check = checked_pipeline_step(scene, k, backward, args, overlap=not args.no_overlap, pipeline=pipeline)
     sync = torch.cuda.synchronize
-    elapsed, regions = timed_median(step, args.steps, args.warmup, sync, D)
-    out = {"ranks": rank_spread(D), "pipeline_check": pipe_check, "timed_regions_ms_per_step": regions,
+    elapsed, regions = timed_headline(step, args, sync, D)
+    out = {"ranks": rank_spread(D), "pipeline_check": pipe_check, "timed_regions_ms_per_step": regions, "timed_regions_note": REGIONS_NOTE[args.full],
            "metric": "points/sec through KNN+group+PointTransformer(vector attention)+CBL block, S3DIS N=%d K=%d" % (n, k),
            "value": n * args.steps * world / elapsed, "unit": "points/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": elapsed / args.steps * 1e3, "host_issue_ms_per_step": timed_region.issue_s / args.steps * 1e3, "higher_is_better": True,
@@ -1157,7 +1230,9 @@ def run_pt(args, D, world, rank, local):
                                   % (n, k, c, "forward + backward of the block" if backward else "forward block + CBL head", " -> ".join(step.names)),
                       "block": "Point Transformer layer (blocks.py:31-44: share_planes 8, train-mode BatchNorms, seeded weights) in place of KPConv",
                       "parallelism": "scene-per-GPU replicas x%d (no data-path collective)" % world, "issue": step.note}}
-    if args.no_extra:
+    if args.dump_outputs and rank == 0:
+        out["dumped_outputs"] = dump_outputs(step.last_state(), n, args.dump_outputs)
+    if args.no_extra or not args.full:
         if rank == 0:
             print(json.dumps(out), flush=True)
         return finish(world)
@@ -1215,6 +1290,9 @@ def finish(world):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse(argv)
+    if args.dump_outputs and (args.workload != "block" or args.host_dry_run):
+        sys.stderr.write("bench.py: --dump-outputs writes the outputs of the block's step (the default workload, --block pt)\n")
+        return 2
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn(args, argv)
     from contrastboundary_amd import distributed as D

@@ -22,7 +22,7 @@ def _run(cmd, env=None):
 
 
 def test_bench_json_contract_and_rccl_allreduce_leg():
-    r, lines = _run([sys.executable, "bench.py", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--allreduce-single"])
+    r, lines = _run([sys.executable, "bench.py", "--full", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--allreduce-single"])
     assert r.returncode == 0, r.stderr[-3000:]
     assert len(lines) == 1
     out = json.loads(lines[0])

@@ -129,7 +129,7 @@ def test_bench_convnet_json_contract():
     e = dict(os.environ)
     for key in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         e.pop(key, None)
-    r = subprocess.run([sys.executable, "bench.py", "--workload", "convnet", "--points", "60000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--workload", "convnet", "--points", "60000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=900, env=e, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

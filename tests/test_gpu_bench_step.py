@@ -116,3 +116,42 @@ def test_every_pipeline_layout_computes_the_step(oracle, layout, slots):
         check_state(st, oracle, True)
     with pytest.raises(ValueError):
         hotpath.Pipeline(step.sched, layout="no such layout")
+
+
+def test_plain_bench_run_dumps_what_its_last_step_computed(oracle, tmp_path):
+    """`python bench.py --steps K --warmup W --dump-outputs DIR` as every change is measured: ONE region of exactly K timed steps, the headline fields and
+    nothing of what `--full` adds, and DIR/<name>.npy of the last timed step held against the oracles like the step itself (the largest outputs as the
+    seeded sample of rows in rows.npy, the K=36 rows sorted)"""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {key: v for key, v in os.environ.items() if key not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    steps = 7
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", "2", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600, env=env, cwd=root)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["steps"] == steps and out["warmup"] == 2 and out["n_gpus"] == 1 and out["unit"] == "points/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert abs(out["value"] - N * steps / (out["ms_per_step"] * steps * 1e-3)) < 1e-6 * out["value"]
+    assert len(out["timed_regions_ms_per_step"]) == 1 and abs(out["timed_regions_ms_per_step"][0] - out["ms_per_step"]) < 1e-4
+    assert not {"roofline", "forward_only", "no_pipeline", "grad_allreduce", "cpu_baseline", "pt_block", "convnet", "train_step", "stage_shapes"} & set(out)
+
+    files = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert set(files) == set(out["dumped_outputs"]) and all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(os.path.getsize(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)) <= 64 << 20
+    rows = files["rows"].astype(np.int64) if "rows" in files else np.arange(N)
+    want = lambda name, a: a[rows] if a.shape[0] == N and files[name].shape[0] != N else a
+    close = lambda name, a: np.allclose(files[name], want(name, a), rtol=1e-4, atol=1e-4 * np.abs(a).max())
+    assert np.array_equal(files["idx"], want("idx", oracle["idx"])), "K=16 neighbour indices differ from the oracle"
+    assert np.array_equal(files["dist2"].view(np.uint32), want("dist2", oracle["d2"]).view(np.uint32)), "K=16 squared distances differ"
+    assert np.array_equal(files["cbl_idx"], want("cbl_idx", np.sort(oracle["widx"], 1))), "K=36 neighbour sets differ from the oracle"
+    assert np.array_equal(files["grouped"], want("grouped", oracle["grouped"])), "grouped tensor differs"
+    assert close("kpconv", oracle["kpconv"]), "KPConv output beyond 1e-4"
+    assert abs(float(files["cbl_loss"]) - oracle["loss"]) < 1e-4 * max(1.0, abs(oracle["loss"])), "CBL loss beyond 1e-4"
+    assert close("cbl_grad", oracle["grad"]), "CBL gradient beyond 1e-4"
+    assert np.array_equal(files["grad_feat_group"], want("grad_feat_group", oracle["g_group"])), "grouping backward (K4) differs"
+    assert close("grad_feat_kpconv", oracle["g_feat_kp"]) and close("grad_kernel_weights", oracle["g_kw"]), "KPConv gradients beyond 1e-4"

@@ -8,7 +8,7 @@ mkdir -p $O
 cd $GRAFT_REPO_ROOT
 for rep in 1 2 3; do
   for v in ${VALS//,/ }; do
-    env $VAR=$v timeout 300 python bench.py "$@" > $O/run_${v}_$rep.json 2> $O/run_${v}_$rep.err
+    env $VAR=$v timeout 300 python bench.py --full "$@" > $O/run_${v}_$rep.json 2> $O/run_${v}_$rep.err
     python - "$O/run_${v}_$rep.json" "$VAR=$v" <<'PY'
 import json, sys
 try:

@@ -34,11 +34,11 @@ if os.path.exists(g):
 json.dump(d, open(O + "/pmc_traffic.json", "w"), indent=1); json.dump(d, open("profiles/r04_pmc_traffic.json", "w"), indent=1)
 PY
 # ---- the three bench lines (the default one carries the pt_block and convnet legs) and their kernel statistics
-timeout 900 python bench.py --steps 50 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
-timeout 400 python bench.py --block pt --steps 30 --warmup 5 --no-cpu-baseline > $O/bench_pt.json 2> $O/bench_pt.err; echo "bench pt rc=$?"
-timeout 600 python bench.py --workload convnet --steps 20 --warmup 3 > $O/bench_convnet.json 2> $O/bench_convnet.err; echo "bench convnet rc=$?"
+timeout 900 python bench.py --full --steps 50 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+timeout 400 python bench.py --full --block pt --steps 30 --warmup 5 --no-cpu-baseline > $O/bench_pt.json 2> $O/bench_pt.err; echo "bench pt rc=$?"
+timeout 600 python bench.py --full --workload convnet --steps 20 --warmup 3 > $O/bench_convnet.json 2> $O/bench_convnet.err; echo "bench convnet rc=$?"
 prof() { tag=$1; shift; (cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$tag -o $tag -- "$@" > $O/prof_$tag.log 2>&1; echo "rocprof $tag rc=$?"); f=$(find $O/prof_$tag -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $O/${tag}_kernel_stats.csv; rm -rf $O/prof_$tag; }
-prof bench python $GRAFT_REPO_ROOT/bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-legs --no-gather-200k
+prof bench python $PWD/bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-legs --no-gather-200k
 prof bench_pt python $GRAFT_REPO_ROOT/bench.py --block pt --steps 30 --warmup 5 --no-cpu-baseline --no-extra
 prof bench_convnet python $GRAFT_REPO_ROOT/bench.py --workload convnet --steps 20 --warmup 3 --no-cpu-baseline --no-extra
 prof pt_layer python $GRAFT_REPO_ROOT/tools/pt_layer_time.py 40960 16 64

@@ -39,11 +39,11 @@ bash tools/gpu_pmc_mix.sh $COMMIT r05_headline > $O/pmc_mix_headline.txt 2>&1; c
 bash tools/gpu_pmc_any.sh r05_pt_layer "^pt_|^triple" python $GRAFT_REPO_ROOT/tools/pt_layer_time.py 40960 16 64 > $O/pmc_pt_layer.txt 2>&1; cp gpurun_out/pmc_r05_pt_layer/pmc_mix.json $O/pmc_pt_layer.json 2>/dev/null
 bash tools/gpu_pmc_any.sh r05_kpconv "kpconv|query_group|grouping_bwd|contrast" python $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra --no-pipeline > $O/pmc_kpconv.txt 2>&1; cp gpurun_out/pmc_r05_kpconv/pmc_mix.json $O/pmc_kpconv.json 2>/dev/null
 # ---- the three bench lines (the default one carries the pt_block and convnet legs) and their kernel statistics
-timeout 900 python bench.py --steps 50 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
-timeout 400 python bench.py --block pt --steps 30 --warmup 5 --no-cpu-baseline > $O/bench_pt.json 2> $O/bench_pt.err; echo "bench pt rc=$?"
-timeout 600 python bench.py --workload convnet --steps 40 --warmup 5 > $O/bench_convnet.json 2> $O/bench_convnet.err; echo "bench convnet rc=$?"
+timeout 900 python bench.py --full --steps 50 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+timeout 400 python bench.py --full --block pt --steps 30 --warmup 5 --no-cpu-baseline > $O/bench_pt.json 2> $O/bench_pt.err; echo "bench pt rc=$?"
+timeout 600 python bench.py --full --workload convnet --steps 40 --warmup 5 > $O/bench_convnet.json 2> $O/bench_convnet.err; echo "bench convnet rc=$?"
 prof() { tag=$1; shift; (cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$tag -o $tag -- "$@" > $O/prof_$tag.log 2>&1; echo "rocprof $tag rc=$?"); f=$(find $O/prof_$tag -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $O/${tag}_kernel_stats.csv; rm -rf $O/prof_$tag; }
-prof bench python $GRAFT_REPO_ROOT/bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-legs --no-gather-200k
+prof bench python $PWD/bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-legs --no-gather-200k
 prof bench_pt python $GRAFT_REPO_ROOT/bench.py --block pt --steps 30 --warmup 5 --no-cpu-baseline --no-extra
 prof bench_convnet python $GRAFT_REPO_ROOT/bench.py --workload convnet --steps 20 --warmup 3 --no-cpu-baseline --no-extra
 prof pt_layer python $GRAFT_REPO_ROOT/tools/pt_layer_time.py 40960 16 64
