@@ -3,8 +3,10 @@
 Same constructor arguments (head_cfg, config), same forward(output, target, stage_list) -> list of scalar losses (one per
 stage of head_cfg.stage), same numbers.  The whole of point_contrast (:185-246) after the two knnquery calls is ONE fused HIP
 kernel forward and one backward (csrc/cbl.hip) instead of ~15 torch ops, 4 materialised (m,K-1,.) tensors and a host sync.
-Supported head options = the shipped config (config/s3dis/origin_multi-...-contrast-Ua-softnn-latent-label-l2-w.1.yaml:60-68):
-pos='cnt', dist='l2', contrast='softnn', sample='label', no projection MLP; anything else raises NotImplementedError.
+Supported head options = what the reference itself runs: pos='cnt', dist='l2', contrast='softnn' | 'nce', sample='label', an optional
+projection MLP, and every ftype of get_ftype (model/utils.py:59-68): 'latent', 'f_out' / 'out' (the stage widths 32 ... 512), 'logits' (13 / 20).
+The pair kernels take feature rows of any width d >= 1 up to 4096 floats (include/cbl_amd.h CBL_CONTRAST_PAIRS_MAX_D); anything else raises
+NotImplementedError.
 """
 import ctypes
 import re
@@ -97,14 +99,12 @@ def _pairs_backward_atomic(features, coef, own, stats, neighbor_idx, grad_loss, 
 
 
 def point_contrast(features, labels, neighbor_idx, temperature=1.0, weight=0.1, return_mask=False, transposed=None, contrast="softnn"):
-    """features (m,d) f32, labels (m,ncls) f32 soft/one-hot OR (m,) int class ids, neighbor_idx (m,nsample) i32 incl. the self column
+    """features (m,d) f32 contiguous, any width d >= 1 up to 4096, labels (m,ncls) f32 soft/one-hot OR (m,) int class ids, neighbor_idx (m,nsample) i32 incl. the self column
     -> scalar loss (device tensor, differentiable w.r.t. features).  transposed: pointops.neighbor_transpose(neighbor_idx, m) if the
     caller already has it (it is looked up in / built into the active neighbour cache otherwise).
     contrast: 'softnn' (heads.py:151-165) or 'nce' (:167-183: one term per positive pair, mean over all of them)."""
     if contrast not in ("softnn", "nce"):
         raise NotImplementedError(f"point_contrast: contrast={contrast!r}")
-    if features.shape[1] not in (4, 8, 16, 32, 64):
-        raise NotImplementedError(f"point_contrast: feature width {features.shape[1]} (the fused head covers 4, 8, 16, 32, 64)")
     m = features.shape[0]
     if labels.dim() == 2:
         amax = torch.empty(m, dtype=torch.int32, device=features.device)
@@ -141,13 +141,6 @@ class ContrastHead(torch.nn.Module):
             from .blocks import MLPbyOps
             self.project = torch.nn.ModuleDict({f"{n}{i}": MLPbyOps(head_cfg.project, config.base_fdim * 2 ** i, d_out=config.base_fdim)
                                                 for n, i in self.stages})            # heads.py:88-92
-        if self.ftype != "latent" and self.project is None:
-            # 'f_out' / 'out' hand the head the stage widths (pointtransformer_seg.py: planes 32 ... 512); the fused kernels cover rows of 4 ... 64 floats
-            planes = [int(v) for v in config.planes] if "planes" in config else [32, 64, 128, 256, 512]
-            bad = [(n, i) for n, i in self.stages if planes[i] not in (4, 8, 16, 32, 64)]
-            if bad:
-                raise NotImplementedError(f"ContrastHead ftype={head_cfg.ftype!r}: stages {bad} are wider than the 64 floats per row the fused HIP "
-                                          "path covers (the shipped config contrasts the 32-d 'latent' features)")
         self.temperature = float(head_cfg.temperature) if "temperature" in head_cfg and head_cfg.temperature is not None else 1.0
         self.weight = float(head_cfg.weight[1:])                         # 'w.1' -> 0.1, heads.py:241-243
 
@@ -266,6 +259,7 @@ class _TFContrastPairs(Function):
 
 
 ROLE_LABEL, ROLE_POS, ROLE_NEG, ROLE_NEG_REJECT = 0, 1, 2, 3               # include/cbl_amd.h CBL_ROLE_*
+PER_POINT_WIDTHS = (4, 8, 16, 32, 64)                                      # the feature widths of the per-point kernels (cbl_tf_contrast_*, cbl.hip)
 
 
 def tf_sample_columns(neighbors, sample, rand_idx=None, batches_len=None, generator=None):
@@ -338,8 +332,9 @@ def tf_contrast(features, labels, neighbors, temperature=1.0, weight=0.1, return
             raise ValueError("labelkl: labels must be (N, ncls <= 255) distributions")
     # Every configuration takes the pair kernels: mining + loss + per-pair coefficients in one pass, the neighbour half of the gradient as a gather
     # over the transposed table of `neighbors` (the table AdaptiveWeight's backward builds for the same tensor: cached, not rebuilt) — no float
-    # atomics, run-to-run deterministic.  `atomic_scatter=True` keeps round 1's kernels reachable (cbl_tf_contrast_*: gradient by row atomics).
-    if not atomic_scatter or contrast == "nce" or separate or not plain_sample:
+    # atomics, run-to-run deterministic.  `atomic_scatter=True` keeps round 1's kernels reachable (cbl_tf_contrast_*: gradient by row atomics) at the
+    # widths they cover; other widths take the pair kernels.
+    if not atomic_scatter or contrast == "nce" or separate or not plain_sample or features.shape[1] not in PER_POINT_WIDTHS:
         if plain_sample:
             samples, roles, valid = neighbors.contiguous(), None, None
         else:

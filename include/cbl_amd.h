@@ -35,6 +35,7 @@ extern "C" {
 #define CBL_ERR_UNSUPPORTED (-3)
 
 #define CBL_KNN_MAX_NSAMPLE 1024   /* knnquery_cuda_kernel.cu:89-90: float best_dist[1024] */
+#define CBL_CONTRAST_PAIRS_MAX_D 4096   /* widest feature row of cbl_contrast_pairs_* (the TF head's widest stage is 2304) */
 
 /* library / build identification (host only) */
 const char* cbl_version(void);            /* e.g. "cbl_amd 0.1 gfx950" */
@@ -257,7 +258,8 @@ int cbl_subscene_label(int m, int kr, int num_classes, const long long* target, 
 int cbl_label_argmax(int m, int num_classes, const float* labels, int* amax, void* stream);
 
 /* F5  ContrastHead.point_contrast  pytorch/model/heads.py:185-246 with pos='cnt', dist='l2', contrast='softnn'
- *   features (m,d) f32 (d in {4,8,16,32,64}, 16-byte aligned), amax (m) i32 = argmax of the (sub-scene) label,
+ *   features (m,d) f32 (d in {4,8,16,32,64}, 16-byte aligned: this per-point entry and the others of cbl.hip — cbl_point_contrast_*,
+ *   cbl_tf_contrast_* — keep this width set; cbl_contrast_pairs_* below take any width), amax (m) i32 = argmax of the (sub-scene) label,
  *   neighbor_idx (m,nsample) i32 from cbl_knnquery on the stage's own points (column 0 = self, dropped; nsample <= 65)
  *   -> per_point (m) f32 loss of each point (0 where masked), point_mask (m) i32 (1 = has both positive and negative
  *      neighbours), stats (2) f32 = {sum of per-point losses, #masked-in points}, loss (1) f32 = weight * mean
@@ -306,7 +308,10 @@ int cbl_contrast_grad_scale(long long total, const float* grad_unit, const float
  *             grad_loss * weight / count;  `order` (m, NULL = none) = processing sequence, values do not depend on it
  *   backward: grad_features[t] = (grad_own[t] + sum over the pairs p = (i, col) listing t of coef[p] (f_t - f_i)) * grad_loss * weight / count,
  *             a gather over the transposed table of neighbor_idx (cbl_neighbor_transpose with n = m, order_dst = order)
- * d in {4, 8, 16, 32, 64}, nsample <= 65. */
+ * Width contract of cbl_contrast_pairs_forward / _forward_samples / _backward / _backward_atomic: any d >= 1 up to CBL_CONTRAST_PAIRS_MAX_D
+ * (4096); features, grad_own and grad_features 16-byte aligned when d % 4 == 0 (rows read as float4), 4-byte aligned otherwise
+ * (CBL_ERR_BAD_ARG if not); CBL_ERR_UNSUPPORTED only for d > CBL_CONTRAST_PAIRS_MAX_D.  d in {4, 8, 16, 32, 64} runs the kernels that hold a
+ * row in one load per lane, every other width the chunked ones (16 lanes per row, 64 or 16 floats per chunk).  nsample <= 65. */
 int cbl_contrast_pairs_forward(int m, int n_valid, int flags, int nsample, int d, const float* features, const void* labels, int num_classes,
                                float kl_threshold, const int* neighbor_idx, const int* order, float temperature, float weight,
                                float* per_point, int* point_mask, float* stats, float* loss, float* coef, float* grad_own, void* stream);
@@ -342,7 +347,8 @@ int cbl_contrast_pairs_backward_atomic(int m, int n_valid, int nsample, int d, c
  *      neighbourhoods (ids >= n_valid are the search's shadow padding; negative hard labels = ignored points):
  *   features (m,d), labels (n_valid >= m rows, i32 hard label per point, from point_labels or cbl_tf_scene_label + cbl_label_argmax),
  *   neighbors (m,nsample) i32 incl. the self column 0 (dropped, :560) -> per_point / point_mask / stats / loss as cbl_point_contrast_forward.
- *   Differences from the pytorch head, all reproduced: valid mask (:540-545), dist = sqrt(max(.,1e-12)) (:184-185), max-shift over all columns (:752). */
+ *   Differences from the pytorch head, all reproduced: valid mask (:540-545), dist = sqrt(max(.,1e-12)) (:184-185), max-shift over all columns (:752).
+ *   d in {4,8,16,32,64}, 16-byte aligned, as cbl_point_contrast_forward (other widths: cbl_contrast_pairs_forward with flags bit 0). */
 int cbl_tf_contrast_forward(int m, int n_valid, int nsample, int d, const float* features, const int* labels, const int* neighbors,
                             float temperature, float weight, float* per_point, int* point_mask, float* stats, float* loss, void* stream);
 int cbl_tf_contrast_backward(int m, int n_valid, int nsample, int d, const float* features, const int* labels, const int* neighbors,
