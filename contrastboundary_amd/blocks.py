@@ -12,7 +12,7 @@ changes is how the K-neighbour part runs:
     the following ReLU folded in (`dense.batch_norm`);
   * the four Linear layers that act on (n*K) rows with widths 3 / C/8 (linear_p, linear_w) run as streaming kernels
     (`dense.linear`, csrc/skinny_linear.hip): as library GEMMs they were half of a layer's time.
-The per-point dense layers (q/k/v Linear, BatchNorm, ReLU, softmax over K) stay torch (rocBLAS / elementwise).
+The per-point q / k / v Linear layers run through `dense.triple_linear` (csrc/skinny_linear.hip at every stage width); the remaining per-point layers stay torch.
 """
 import torch
 import torch.nn as nn
@@ -50,7 +50,7 @@ class PointTransformerLayer(nn.Module):
                 raise ValueError(f"idx: expected a ({x.shape[0]}, {int(self.nsample)}) table on {x.device}, got {tuple(idx.shape)} on {idx.device}")
         wide = self.fused and self.fused not in ("split", "ops") and pt_layer.supported_wide(self, x, idx, p)
         if wide and self.fused != "qkv3" and all(l.bias is not None and l.weight.shape == (self.out_planes, self.out_planes) for l in (self.linear_q, self.linear_k, self.linear_v)):
-            # the wide stages: projections and everything behind them as one node (one batched product for q / k / v each way, then cbl_pt_layer_wide_*)
+            # the wide stages: projections and everything behind them as one node (cbl_triple_linear_* for q / k / v, then cbl_pt_layer_wide_*)
             return pt_layer.attention_wide_projected(self, p, x, idx)
         x_q, x_k, x_v = dense.triple_linear(x, self.linear_q, self.linear_k, self.linear_v)                        # :33, one launch per direction
         if self.fused and self.fused != "split" and pt_layer.supported(self, x, idx, p):

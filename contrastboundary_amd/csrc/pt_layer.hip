@@ -1496,6 +1496,12 @@ __global__ __launch_bounds__(256) void pw_bn_apply_kernel(long long total, int G
     }
 }
 
+// zero fill of the scatter targets as a kernel of this library (a node like every other of a captured step)
+__global__ __launch_bounds__(256) void pw_zero_kernel(long long total, float* __restrict__ p)
+{
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) p[e] = 0.f;
+}
+
 struct PwWs { float *part_p, *part_g, *part_n, *part_d, *bc_g, *logits, *glogit, *pre, *gw2, *gp1a, *gp1b, *w3c2, *b3c2, *gba2; void* attn; size_t attn_bytes; size_t bytes; };
 PwWs pw_workspace(char* base, int n, int K, int C)
 {
@@ -1577,9 +1583,13 @@ CBL_EXPORT int cbl_pt_layer_wide_backward(int n, int K, int C, const float* x_q,
     const unsigned gp = pt_pair_grid(np);
     int rc;
     // the two scatters (d x_k, d x_v) of the wide kernels are float atomics: zero their targets
+    const long long nc = (long long)n * C;
     if (g_xv == g_xk + (size_t)n * C) {                             // one buffer (the Python mirror allocates them together): one fill
-        if (hipMemsetAsync(g_xk, 0, 2 * sizeof(float) * (size_t)n * C, st) != hipSuccess) return cbl_status();
-    } else if (hipMemsetAsync(g_xk, 0, sizeof(float) * (size_t)n * C, st) != hipSuccess || hipMemsetAsync(g_xv, 0, sizeof(float) * (size_t)n * C, st) != hipSuccess) return cbl_status();
+        hipLaunchKernelGGL(pw_zero_kernel, dim3(cbl_grid_for(2 * nc, 256, 2048)), dim3(256), 0, st, 2 * nc, g_xk);
+    } else {
+        hipLaunchKernelGGL(pw_zero_kernel, dim3(cbl_grid_for(nc, 256, 2048)), dim3(256), 0, st, nc, g_xk);
+        hipLaunchKernelGGL(pw_zero_kernel, dim3(cbl_grid_for(nc, 256, 2048)), dim3(256), 0, st, nc, g_xv);
+    }
     // aggregation backward with the softmax backward inside: d x_v, its share of d p1 / d W3C / d b3C, d logits
     if ((rc = cbl_attn_agg_softmax_backward(n, K, C, G, x_v, idx, p1, W3C, b3C, a, grad_out, g_xv, ws.gp1a, ws.w3c2, ws.b3c2, ws.glogit, ws.attn, ws.attn_bytes, stream))) return rc;
     // Linear(G, G), ReLU, BN_g backward

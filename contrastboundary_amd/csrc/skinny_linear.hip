@@ -584,6 +584,250 @@ __global__ __launch_bounds__(1024) void triple_linear_wgrad_finalize_kernel(int 
 
 constexpr int TL_WGRAD_BLOCKS = 256;
 
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// The same three projections at the WIDE stages (C = 128 | 256 | 512; (n, C) = (2560, 128), (640, 256), (160, 512) per scene: 126 M multiply-adds per
+// direction at every stage, ~120 MFMAs per SIMD if spread over the chip — launch and latency, not arithmetic).  A lane of the kernels above keeps
+// 3 C^2 / 64 weight operands in registers (12 288 at C = 512), so these are tiled products with both operands staged in LDS in panels of KP
+// contraction steps: 16-byte coalesced loads of the next panel into registers while the MFMAs of this one run, then one store + barrier.
+// The contraction index is walked in the MFMA's own order (step s, lane quarter kq: k = 4 s + kq); every LDS read is a ds_read_b32 whose 64 lanes hit
+// 64 different banks (row strides = 4 or 16 mod 64 floats).
+//   rows kernel, forward (blockIdx.z = the projection) and input gradient (the three projections walked one after the other into the SAME accumulators):
+//     a workgroup owns 16 MR rows x (64 / KS) columns; its four waves are (4 / KS) column tiles x KS shares of every panel's steps, the shares summed through
+//     LDS in wave order (fixed: bit-identical from call to call).  MR row tiles per wave = MR independent accumulator chains (MR = 1: two, by step parity —
+//     the MFMA's dependent latency is 40 cycles, its issue interval 32).  The host picks MR per shape so that >= ~240 workgroups exist; forward KS = 1,
+//     input gradient KS = 4 (16-column tiles: its contraction is three times as long and only rows x columns tile it).  KP = 128 for 64-row workgroups
+//     (67 KB of LDS, two per compute unit); with 16 / 32 rows — the one-scene shapes, about one workgroup per compute unit, where the time is the chain of
+//     panel loads — 256 (forward, <= 100 KB) up to the whole width (input gradient with 16 rows, <= 69 KB).
+//   weight gradient: a workgroup owns a 64 x 64 tile of one projection's grad_weight over one chunk of rows (>= 128 rows, at most tw_max_chunks(C) chunks:
+//     the partials stay within 25 MB at every width), panels of 64 rows of grad_y / x columns in LDS (40 KB); the workgroups of the first column tile also sum
+//     grad_y's columns (grad_bias).  One chunk: results go straight to the outputs; more: partials + a combine kernel (fp64 sums in chunk order).
+//   Measured (hipGraph replays, forward + backward, us): profiles/triple_linear_wide_time.json; registers / LDS / occupancy: profiles/triple_linear_wide_resources.txt.
+constexpr int TW_KP = 128;                                          // k-contiguous LDS rows: KP + 4 floats (stride = 4 mod 64 banks, 16-byte aligned)
+
+#define TW_PICK(a, p) ((p) == 0 ? (a)[0] : ((p) == 1 ? (a)[1] : (a)[2]))    // a kernel argument's array of three pointers at a run-time index, without an indexed copy of it
+
+template <int C, int MR, int KS, bool DGRAD>
+__global__ __launch_bounds__(256) void triple_wide_rows_kernel(long long rows, RlTriple t3, float* __restrict__ gx)
+{
+    constexpr int TM = 16 * MR, NCT = 4 / KS, TN = 16 * NCT, NACC = MR == 1 ? 2 : 1;
+    // the panel: 128 contraction steps where many workgroups share a compute unit; with 16 / 32 rows (the one-scene shapes: ~1 workgroup per compute unit, the
+    // time is the chain of panel loads) up to a whole projection, so that fewer loads follow one another
+    constexpr int KP = DGRAD ? (MR == 1 ? C : (MR == 2 && C >= 256 ? 256 : TW_KP)) : (MR <= 2 && C >= 256 ? 256 : TW_KP), LDA = KP + 4;
+    constexpr int LDB = DGRAD ? (TN == 16 ? 16 : TN + 16) : LDA;  // DGRAD: B panel k-major (rows of W), stride = 16 | 48 mod 64 banks
+    constexpr int BROWS = DGRAD ? KP : TN;
+    constexpr int NA = TM * (KP / 4) / 256, NB = TN * (KP / 4) / 256, KPANELS = C / KP, NPANEL = (DGRAD ? 3 : 1) * KPANELS;
+    constexpr int SPW = (KP / 4) / KS;                              // MFMA steps of a panel per wave
+    __shared__ __attribute__((aligned(16))) float As[TM * LDA];
+    __shared__ __attribute__((aligned(16))) float Bs[BROWS * LDB];
+    __shared__ float red[KS > 1 ? (KS - 1) * NCT * MR * 256 : 1];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = lane & 15, kq = lane >> 4, ct = wave % NCT, ks = wave / NCT;
+    const long long r0 = (long long)blockIdx.x * TM;
+    const int c0 = blockIdx.y * TN;
+    rl_f32x4 ra[NA], rb[NB];                                      // (as HIP's float4 struct these arrays stay in scratch)
+    rl_f32x4 acc[MR][NACC];
+#pragma unroll
+    for (int m = 0; m < MR; m++)
+#pragma unroll
+        for (int j = 0; j < NACC; j++) acc[m][j] = rl_f32x4{0.f, 0.f, 0.f, 0.f};
+    // one place loads (panel q + 1 into registers), so the trip for q = -1 only loads: the 16-byte loads stay in flight while panel q's MFMAs run
+    for (int q = -1; q < NPANEL; q++) {
+        if (q >= 0) {
+            __syncthreads();                                        // the previous panel is consumed
+#pragma unroll
+            for (int i = 0; i < NA; i++) {
+                const int e = tid + 256 * i, row = e / (KP / 4), c4 = e % (KP / 4);
+                *reinterpret_cast<rl_f32x4*>(&As[row * LDA + 4 * c4]) = ra[i];
+            }
+#pragma unroll
+            for (int i = 0; i < NB; i++) {
+                const int e = tid + 256 * i;
+                if (DGRAD) { const int kr = e / (TN / 4), c4 = e % (TN / 4); *reinterpret_cast<rl_f32x4*>(&Bs[kr * LDB + 4 * c4]) = rb[i]; }
+                else       { const int nr = e / (KP / 4), c4 = e % (KP / 4); *reinterpret_cast<rl_f32x4*>(&Bs[nr * LDB + 4 * c4]) = rb[i]; }
+            }
+            __syncthreads();
+        }
+        if (q + 1 < NPANEL) {
+            const int p = DGRAD ? (q + 1) / KPANELS : (int)blockIdx.z, k0 = ((q + 1) % KPANELS) * KP;
+            const float* __restrict__ in = TW_PICK(t3.in, p);
+            const float* __restrict__ w = TW_PICK(t3.w, p);
+#pragma unroll
+            for (int i = 0; i < NA; i++) {
+                const int e = tid + 256 * i, row = e / (KP / 4), c4 = e % (KP / 4);
+                const long long gr = min(r0 + row, rows - 1);             // rows past the end: a copy of the last row, their results are not stored
+                ra[i] = *reinterpret_cast<const rl_f32x4*>(in + gr * C + k0 + 4 * c4);
+            }
+#pragma unroll
+            for (int i = 0; i < NB; i++) {
+                const int e = tid + 256 * i;
+                if (DGRAD) { const int kr = e / (TN / 4), c4 = e % (TN / 4); rb[i] = *reinterpret_cast<const rl_f32x4*>(w + (size_t)(k0 + kr) * C + c0 + 4 * c4); }
+                else       { const int nr = e / (KP / 4), c4 = e % (KP / 4); rb[i] = *reinterpret_cast<const rl_f32x4*>(w + (size_t)(c0 + nr) * C + k0 + 4 * c4); }
+            }
+        }
+        if (q < 0) continue;
+#pragma unroll
+        for (int s2 = 0; s2 < SPW; s2++) {
+            const int k = 4 * (ks * SPW + s2) + kq;
+            const float b = DGRAD ? Bs[k * LDB + 16 * ct + n] : Bs[(16 * ct + n) * LDB + k];
+#pragma unroll
+            for (int m = 0; m < MR; m++)
+                acc[m][s2 % NACC] = __builtin_amdgcn_mfma_f32_16x16x4f32(As[(16 * m + n) * LDA + k], b, acc[m][s2 % NACC], 0, 0, 0);
+        }
+    }
+    if (NACC == 2) {
+#pragma unroll
+        for (int m = 0; m < MR; m++) acc[m][0] += acc[m][NACC - 1];
+    }
+    if (KS > 1) {                                                   // the KS shares of a column tile: shares 1 .. KS - 1 through LDS, added by share 0 in that order
+        if (ks > 0) {
+#pragma unroll
+            for (int m = 0; m < MR; m++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) red[(((ks - 1) * NCT + ct) * MR + m) * 256 + 64 * r + lane] = acc[m][0][r];
+        }
+        __syncthreads();
+        if (ks > 0) return;
+#pragma unroll
+        for (int j = 1; j < KS; j++)
+#pragma unroll
+            for (int m = 0; m < MR; m++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) acc[m][0][r] += red[(((j - 1) * NCT + ct) * MR + m) * 256 + 64 * r + lane];
+    }
+    // D[4 (lane / 16) + r][lane % 16] in acc[m][0][r]
+    const int col = c0 + 16 * ct + n;
+    float* __restrict__ out = DGRAD ? gx : TW_PICK(t3.out, blockIdx.z);
+    const float* bias = DGRAD ? nullptr : TW_PICK(t3.b, blockIdx.z);
+    const float bv = bias ? bias[col] : 0.f;
+#pragma unroll
+    for (int m = 0; m < MR; m++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const long long orow = r0 + 16 * m + 4 * kq + r;
+            if (orow < rows) out[orow * C + col] = acc[m][0][r] + bv;
+        }
+}
+
+constexpr int TW_WT = 64, TW_WROWS = 64, TW_LDW = TW_WT + 16;        // weight gradient: output tile edge, rows per LDS panel, LDS row stride (16 mod 64 banks)
+inline int tw_max_chunks(int C) { return C == 128 ? 64 : (C == 256 ? 32 : 8); }
+
+// dst = partial + (projection * nchunks + chunk) * (C^2 + C)  (partial != NULL)  or the outputs themselves (one chunk)
+template <int C>
+__global__ __launch_bounds__(256) void triple_wide_wgrad_kernel(long long rows, long long chunk_rows, const float* __restrict__ x, RlTriple t3, float* __restrict__ partial)
+{
+    constexpr int TPR = C / TW_WT, WIDTH = C * C + C;
+    __shared__ __attribute__((aligned(16))) float Gs[TW_WROWS * TW_LDW];      // grad_y[r][o0 ..]
+    __shared__ __attribute__((aligned(16))) float Xs[TW_WROWS * TW_LDW];      // x[r][c0 ..]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = lane & 15, kq = lane >> 4;
+    const int o0 = (blockIdx.x / TPR) * TW_WT, c0 = (blockIdx.x % TPR) * TW_WT, p = blockIdx.z;
+    const bool sums = c0 == 0 && tid < TW_WT;                       // this lane also sums column o0 + tid of grad_y
+    const float* __restrict__ gy = TW_PICK(t3.in, p);
+    const long long rbeg = (long long)blockIdx.y * chunk_rows, rend = min(rows, rbeg + chunk_rows);
+    const int npanel = (int)((rend - rbeg + TW_WROWS - 1) / TW_WROWS);
+    constexpr int NL = TW_WROWS * (TW_WT / 4) / 256;
+    rl_f32x4 rg[NL], rx[NL];
+    auto load = [&](int q) {
+#pragma unroll
+        for (int i = 0; i < NL; i++) {
+            const int e = tid + 256 * i, row = e / (TW_WT / 4), c4 = e % (TW_WT / 4);
+            const long long gr = rbeg + (long long)q * TW_WROWS + row;
+            const bool ok = gr < rend;
+            const long long gc = ok ? gr : rend - 1;
+            rg[i] = *reinterpret_cast<const rl_f32x4*>(gy + gc * C + o0 + 4 * c4);
+            rx[i] = *reinterpret_cast<const rl_f32x4*>(x + gc * C + c0 + 4 * c4);
+            if (!ok) { rg[i] = rl_f32x4{0.f, 0.f, 0.f, 0.f}; rx[i] = rl_f32x4{0.f, 0.f, 0.f, 0.f}; }
+        }
+    };
+    rl_f32x4 acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; t++) acc[t] = rl_f32x4{0.f, 0.f, 0.f, 0.f};
+    float bsum = 0.f;
+    load(0);
+    for (int q = 0; q < npanel; q++) {
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < NL; i++) {
+            const int e = tid + 256 * i, row = e / (TW_WT / 4), c4 = e % (TW_WT / 4);
+            *reinterpret_cast<rl_f32x4*>(&Gs[row * TW_LDW + 4 * c4]) = rg[i];
+            *reinterpret_cast<rl_f32x4*>(&Xs[row * TW_LDW + 4 * c4]) = rx[i];
+        }
+        __syncthreads();
+        if (q + 1 < npanel) load(q + 1);
+        // A[m][k] = grad_y[r + k][o0 + 16 wave + m], B[k][n] = x[r + k][c0 + 16 t + n]: the contraction runs over the rows, four per step
+#pragma unroll
+        for (int s2 = 0; s2 < TW_WROWS / 4; s2++) {
+            const int k = 4 * s2 + kq;
+            const float a = Gs[k * TW_LDW + 16 * wave + n];
+#pragma unroll
+            for (int t = 0; t < 4; t++) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, Xs[k * TW_LDW + 16 * t + n], acc[t], 0, 0, 0);
+        }
+        if (sums) {
+            float s = 0.f;
+#pragma unroll 8
+            for (int r = 0; r < TW_WROWS; r++) s += Gs[r * TW_LDW + tid];
+            bsum += s;
+        }
+    }
+    float* __restrict__ dw = partial ? partial + ((size_t)p * gridDim.y + blockIdx.y) * WIDTH : TW_PICK(t3.out, p);
+    // D[m = 4 (lane / 16) + r][n = lane % 16] of tile t = grad_weight[o0 + 16 wave + m][c0 + 16 t + n]
+#pragma unroll
+    for (int t = 0; t < 4; t++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) dw[(size_t)(o0 + 16 * wave + 4 * kq + r) * C + c0 + 16 * t + n] = acc[t][r];
+    if (sums) {
+        float* db = partial ? dw + C * C : const_cast<float*>(TW_PICK(t3.b, p));
+        if (db) db[o0 + tid] = bsum;
+    }
+}
+
+// grad_weight / grad_bias = the chunks' partials summed in chunk order (fp64); plain stores
+__global__ __launch_bounds__(256) void triple_wide_wgrad_combine_kernel(int C, int nchunks, const float* __restrict__ partial, RlTriple t3)
+{
+    const int width = C * C + C, e = blockIdx.x * 256 + threadIdx.x, p = blockIdx.y;
+    if (e >= width) return;
+    const float* src = partial + (size_t)p * nchunks * width + e;
+    double s = 0.0;
+#pragma unroll 4
+    for (int j = 0; j < nchunks; j++) s += (double)src[(size_t)j * width];
+    if (e < C * C) TW_PICK(t3.out, p)[e] = (float)s;
+    else { float* db = const_cast<float*>(TW_PICK(t3.b, p)); if (db) db[e - C * C] = (float)s; }
+}
+
+inline bool tw_wide(int C) { return C == 128 || C == 256 || C == 512; }
+
+// rows per workgroup = 16 MR: the largest of 64 / 32 / 16 that still leaves ~240 workgroups (one per compute unit)
+inline int tw_pick_mr(long long rows, long long col_groups)
+{
+    for (int mr = 4; mr > 1; mr >>= 1) if (((rows + 16 * mr - 1) / (16 * mr)) * col_groups >= 240) return mr;
+    return 1;
+}
+
+template <int C, bool DGRAD>
+int tw_rows_launch(long long rows, const RlTriple& t3, float* gx, hipStream_t st)
+{
+    constexpr int KS = DGRAD ? 4 : 1, TN = 64 / KS, NZ = DGRAD ? 1 : 3;
+    const int mr = tw_pick_mr(rows, (long long)(C / TN) * NZ);
+    const dim3 grid((unsigned)((rows + 16 * mr - 1) / (16 * mr)), C / TN, NZ), blk(256);
+    if (mr == 4)      hipLaunchKernelGGL((triple_wide_rows_kernel<C, 4, KS, DGRAD>), grid, blk, 0, st, rows, t3, gx);
+    else if (mr == 2) hipLaunchKernelGGL((triple_wide_rows_kernel<C, 2, KS, DGRAD>), grid, blk, 0, st, rows, t3, gx);
+    else              hipLaunchKernelGGL((triple_wide_rows_kernel<C, 1, KS, DGRAD>), grid, blk, 0, st, rows, t3, gx);
+    return cbl_status();
+}
+
+template <int C>
+int tw_wgrad_launch(long long rows, const float* x, const RlTriple& t3, float* partial, hipStream_t st)
+{
+    // chunks of >= 128 rows; where the output tiles alone give ~200 workgroups (C = 512) and the rows are few, one chunk: no partials, no combine launch
+    long long nchunks = min((rows + 127) / 128, (long long)tw_max_chunks(C));
+    if (3 * (C / TW_WT) * (C / TW_WT) >= 192 && rows <= 256) nchunks = 1;
+    const long long chunk_rows = ((rows + nchunks - 1) / nchunks + TW_WROWS - 1) / TW_WROWS * TW_WROWS;
+    nchunks = (rows + chunk_rows - 1) / chunk_rows;
+    const dim3 grid((C / TW_WT) * (C / TW_WT), (unsigned)nchunks, 3);
+    hipLaunchKernelGGL(triple_wide_wgrad_kernel<C>, grid, dim3(256), 0, st, rows, chunk_rows, x, t3, nchunks > 1 ? partial : nullptr);
+    if (nchunks > 1)
+        hipLaunchKernelGGL(triple_wide_wgrad_combine_kernel, dim3(cbl_div_up(C * C + C, 256), 3), dim3(256), 0, st, C, (int)nchunks, partial, t3);
+    return cbl_status();
+}
+
 inline bool rl_mfma_ok(int cin, int cout) { return cin % 16 == 0 && cout % 16 == 0 && cin <= 64 && cout <= 64 && cin >= 16 && cout >= 16; }
 // a ragged c_in between 17 and 63 beside a c_out the matrix tiles cover: the padded-in-registers kernels
 inline bool rl_ragged_ok(int cin, int cout) { return cin > 16 && cin < 64 && cin % 16 != 0 && cout % 16 == 0 && cout >= 16 && cout <= 64; }
@@ -724,19 +968,26 @@ CBL_EXPORT int cbl_skinny_linear_backward_weight(long long rows, int cin, int co
     return cbl_status();
 }
 
-// ---- the three projections of PointTransformerLayer as one launch per direction (blocks.py:33; C = 32 | 64) ----
+// ---- the three projections of PointTransformerLayer as one launch per direction (blocks.py:33; C = 32 | 64, and the tiled kernels at 128 | 256 | 512) ----
 CBL_EXPORT size_t cbl_triple_linear_workspace_bytes(int C)
 {
+    if (tw_wide(C)) return sizeof(float) * 3 * (size_t)tw_max_chunks(C) * ((size_t)C * C + C) + 256;      // 12.7 MB | 25.3 MB | 25.2 MB
     if (C != 32 && C != 64) return 0;
     return sizeof(float) * 3 * (size_t)TL_WGRAD_BLOCKS * ((size_t)C * C + C) + 256;
 }
 
 CBL_EXPORT int cbl_triple_linear_forward(long long rows, int C, const float* x, const float* const* weight3, const float* const* bias3, float* const* y3, void* stream)
 {
-    if (C != 32 && C != 64) return CBL_ERR_UNSUPPORTED;
+    if (C != 32 && C != 64 && !tw_wide(C)) return CBL_ERR_UNSUPPORTED;
     if (rows <= 0 || !x || !weight3 || !y3 || !cbl_host_aligned16(x)) return CBL_ERR_BAD_ARG;
     RlTriple t3;
     for (int p = 0; p < 3; p++) { t3.in[p] = x; t3.w[p] = weight3[p]; t3.b[p] = bias3 ? bias3[p] : nullptr; t3.out[p] = y3[p]; }
+    if (tw_wide(C)) {
+        for (int p = 0; p < 3; p++) if (!weight3[p] || !y3[p] || !cbl_host_aligned16(weight3[p])) return CBL_ERR_BAD_ARG;      // weight rows are read 16 bytes at a time
+        if (C == 128) return tw_rows_launch<128, false>(rows, t3, nullptr, cbl_stream(stream));
+        if (C == 256) return tw_rows_launch<256, false>(rows, t3, nullptr, cbl_stream(stream));
+        return tw_rows_launch<512, false>(rows, t3, nullptr, cbl_stream(stream));
+    }
     const long long tiles = (rows + 15) / 16;
     const dim3 grid((unsigned)min((tiles + 3) / 4, (long long)256)), blk(256);
     if (C == 64) hipLaunchKernelGGL(triple_linear_forward_kernel<64>, grid, blk, 0, cbl_stream(stream), rows, x, t3);
@@ -748,13 +999,23 @@ CBL_EXPORT int cbl_triple_linear_forward(long long rows, int C, const float* x, 
 CBL_EXPORT int cbl_triple_linear_backward(long long rows, int C, const float* x, const float* const* weight3, const float* const* grad_y3, float* grad_x,
                                           float* const* grad_weight3, float* const* grad_bias3, void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (C != 32 && C != 64) return CBL_ERR_UNSUPPORTED;
+    if (C != 32 && C != 64 && !tw_wide(C)) return CBL_ERR_UNSUPPORTED;
     if (rows <= 0 || !x || !weight3 || !grad_y3 || !grad_x || !grad_weight3 || !workspace) return CBL_ERR_BAD_ARG;
     if (workspace_bytes < cbl_triple_linear_workspace_bytes(C)) return CBL_ERR_WORKSPACE;
     for (int p = 0; p < 3; p++) if (!cbl_host_aligned16(grad_y3[p])) return CBL_ERR_BAD_ARG;
     hipStream_t st = cbl_stream(stream);
     RlTriple t3;
     for (int p = 0; p < 3; p++) { t3.in[p] = grad_y3[p]; t3.w[p] = weight3[p]; t3.b[p] = grad_bias3 ? grad_bias3[p] : nullptr; t3.out[p] = grad_weight3[p]; }
+    if (tw_wide(C)) {
+        if (!cbl_host_aligned16(x)) return CBL_ERR_BAD_ARG;
+        for (int p = 0; p < 3; p++) if (!grad_y3[p] || !weight3[p] || !grad_weight3[p] || !cbl_host_aligned16(weight3[p])) return CBL_ERR_BAD_ARG;
+        float* part = reinterpret_cast<float*>(workspace);
+        int rc;
+        if (C == 128)      { rc = tw_rows_launch<128, true>(rows, t3, grad_x, st); if (!rc) rc = tw_wgrad_launch<128>(rows, x, t3, part, st); }
+        else if (C == 256) { rc = tw_rows_launch<256, true>(rows, t3, grad_x, st); if (!rc) rc = tw_wgrad_launch<256>(rows, x, t3, part, st); }
+        else               { rc = tw_rows_launch<512, true>(rows, t3, grad_x, st); if (!rc) rc = tw_wgrad_launch<512>(rows, x, t3, part, st); }
+        return rc;
+    }
     const long long tiles = (rows + 15) / 16;
     const dim3 grid((unsigned)min((tiles + 3) / 4, (long long)256)), blk(256);
     if (C == 64) hipLaunchKernelGGL(triple_linear_dgrad_kernel<64>, grid, blk, 0, st, rows, t3, grad_x);

@@ -102,7 +102,8 @@ def linear(x, weight, bias=None):
 
 
 class _TripleLinear(Function):
-    """x_q, x_k, x_v = linear_q(x), linear_k(x), linear_v(x)  (blocks.py:33) as one launch per direction (cbl_triple_linear_*, C = 32 | 64)"""
+    """x_q, x_k, x_v = linear_q(x), linear_k(x), linear_v(x)  (blocks.py:33) as one launch per direction (cbl_triple_linear_*: C = 32 | 64, and the tiled
+    kernels of the wide stages at C = 128 | 256 | 512)"""
 
     @staticmethod
     def forward(ctx, x, wq, bq, wk, bk, wv, bv):
@@ -131,10 +132,14 @@ class _TripleLinear(Function):
         return gx, gws[0], gbs[0], gws[1], gbs[1], gws[2], gbs[2]
 
 
+WIDE_WIDTHS = (128, 256, 512)       # the wide attention stages: 160 .. 20 480 rows, cbl_triple_linear_* at any number of rows (no library GEMM in front of the layer)
+
+
 def triple_linear(x, lq, lk, lv):
-    """(lq(x), lk(x), lv(x)) for three nn.Linear(C, C) with biases: one launch per direction at C = 32 | 64 on >= MIN_ROWS rows, `linear` x 3 otherwise"""
+    """(lq(x), lk(x), lv(x)) for three nn.Linear(C, C) with biases: one launch per direction at C = 32 | 64 on >= MIN_ROWS rows and at C = 128 | 256 | 512 on
+    any number of rows, `linear` x 3 otherwise.  Same values as F.linear up to fp32 summation order."""
     C = x.shape[-1]
-    ok = (x.dim() == 2 and x.is_cuda and x.dtype == torch.float32 and C in (32, 64) and x.shape[0] >= MIN_ROWS
+    ok = (x.dim() == 2 and x.is_cuda and x.dtype == torch.float32 and ((C in (32, 64) and x.shape[0] >= MIN_ROWS) or (C in WIDE_WIDTHS and x.shape[0] >= 1))
           and all(l.weight.shape == (C, C) and l.bias is not None and l.weight.dtype == torch.float32 for l in (lq, lk, lv)))
     if not ok:
         return apply(lq, x), apply(lk, x), apply(lv, x)

@@ -217,30 +217,40 @@ def adjoin_qkv(module):
 
 
 class PTAttentionWideProjected(Function):
-    """the q / k / v projections (blocks.py:33) and PTAttentionWide as one node: the three Linear(C, C) as ONE batched product each way (forward 1 launch
-    instead of 3; backward d x, d W, d b in 4 instead of 11), their outputs and gradients as slices of one (3, n, C) tensor"""
+    """the q / k / v projections (blocks.py:33) and PTAttentionWide as one node: the three Linear(C, C) through cbl_triple_linear_forward / _backward (the tiled
+    MFMA kernels of csrc/skinny_linear.hip: forward 1 launch; backward d x in 1, d W and d b in 1 or 2), their outputs and gradients as slices of one (3, n, C)
+    tensor.  The entries take the three weights by pointer: adjacent (`adjoin_qkv`) or not, nothing is copied."""
 
     @staticmethod
     def forward(ctx, p, x, idx, bns, wq, bq, wk, bk, wv, bv, *params):
         x, p = x.contiguous(), p.contiguous()
         params = [t.contiguous() for t in params]
-        W3, b3 = _stacked((wq, wk, wv)), _stacked((bq, bk, bv))
+        W, b = [t.contiguous() for t in (wq, wk, wv)], [t.contiguous() for t in (bq, bk, bv)]
         n, C = x.shape
-        qkv = torch.baddbmm(b3.unsqueeze(1), x.unsqueeze(0).expand(3, n, C), W3.transpose(1, 2))        # (3, n, C): x W^T + b per projection
+        L = _lib.lib()
+        qkv = torch.empty((3, n, C), dtype=torch.float32, device=x.device)                             # x W^T + b per projection
+        arr = lambda ts: (ctypes.c_void_p * 3)(*[t.data_ptr() for t in ts])
+        _lib.check(L.cbl_triple_linear_forward(ctypes.c_longlong(n), _i(C), _P(x), arr(W), arr(b), arr(qkv), _lib.stream_of(x)), "cbl_triple_linear_forward")
         out, kept = _wide_forward(p, qkv[0], qkv[1], qkv[2], idx, bns, params)
-        ctx.save_for_backward(x, W3, qkv, idx, *kept, *params)
+        ctx.save_for_backward(x, *W, qkv, idx, *kept, *params)
         return out
 
     @staticmethod
     def backward(ctx, g_out):
-        x, W3, qkv, idx = ctx.saved_tensors[:4]
+        x, wq, wk, wv, qkv, idx = ctx.saved_tensors[:6]
         n, C = x.shape
+        L = _lib.lib()
         g_qkv = torch.empty_like(qkv)
-        g_params = _wide_backward(qkv[0], qkv[1], qkv[2], idx, ctx.saved_tensors[4:11], ctx.saved_tensors[11:], g_out, g_qkv)
-        g_x = torch.bmm(g_qkv, W3).sum(0) if ctx.needs_input_grad[1] else None
-        g_W3 = torch.bmm(g_qkv.transpose(1, 2), x.unsqueeze(0).expand(3, n, C))
-        g_b3 = g_qkv.sum(1)
-        return (None, g_x, None, None, g_W3[0], g_b3[0], g_W3[1], g_b3[1], g_W3[2], g_b3[2], *g_params)
+        g_params = _wide_backward(qkv[0], qkv[1], qkv[2], idx, ctx.saved_tensors[6:13], ctx.saved_tensors[13:], g_out, g_qkv)
+        g_x = torch.empty_like(x)
+        g_W3 = torch.empty((3, C, C), dtype=torch.float32, device=x.device)
+        g_b3 = torch.empty((3, C), dtype=torch.float32, device=x.device)
+        arr = lambda ts: (ctypes.c_void_p * 3)(*[t.data_ptr() for t in ts])
+        from .neighbor_state import scratch
+        ws = scratch(_ws, "qkv", L.cbl_triple_linear_workspace_bytes(_i(C)), x.device)
+        _lib.check(L.cbl_triple_linear_backward(ctypes.c_longlong(n), _i(C), _P(x), arr((wq, wk, wv)), arr(g_qkv), _P(g_x), arr(g_W3), arr(g_b3),
+                                                _P(ws), ctypes.c_size_t(ws.numel()), _lib.stream_of(x)), "cbl_triple_linear_backward")
+        return (None, g_x if ctx.needs_input_grad[1] else None, None, None, g_W3[0], g_b3[0], g_W3[1], g_b3[1], g_W3[2], g_b3[2], *g_params)
 
 
 def attention_wide_projected(layer, p, x, idx):

@@ -578,11 +578,19 @@ int cbl_skinny_linear_backward_input(long long rows, int cin, int cout, const fl
 int cbl_skinny_linear_backward_weight(long long rows, int cin, int cout, const float* x, const float* grad_y, float* grad_weight, float* grad_bias,
                                       void* workspace, size_t workspace_bytes, void* stream);
 
-/* a4: the three per-point projections of the layer, x_q, x_k, x_v = linear_q(x), linear_k(x), linear_v(x)  pytorch/model/blocks.py:33 (nn.Linear(C, C) x 3,
- *     C = 32 | 64), one launch per direction.  weight3 / bias3 / y3 / grad_*3: HOST arrays of 3 device pointers (q, k, v).
- *   forward   y3[p] (rows, C) = x . weight3[p]^T + bias3[p]
+/* a4: the three per-point projections of the layer, x_q, x_k, x_v = linear_q(x), linear_k(x), linear_v(x)  pytorch/model/blocks.py:33 (nn.Linear(C, C) x 3),
+ *     one launch per direction.  weight3 / bias3 / y3 / grad_*3: HOST arrays of 3 device pointers (q, k, v).
+ *   C = 32 | 64 (the full-resolution stages: the weights stay in registers for the launch) and C = 128 | 256 | 512 (the wide stages: tiled products, both
+ *   operands through LDS in panels); every other C: CBL_ERR_UNSUPPORTED.  Any rows >= 1.  fp32 in, fp32 accumulate on v_mfma_f32_16x16x4_f32.
+ *   forward   y3[p] (rows, C) = x . weight3[p]^T + bias3[p]  (bias3 or entries of it may be NULL)
  *   backward  grad_x = sum_p grad_y3[p] . weight3[p] (one pass, accumulated in the MFMA accumulators: no partial tensors, no adds);
- *             grad_weight3[p] (C, C) = grad_y3[p]^T . x; grad_bias3[p] (C) = column sums (array or entries may be NULL).  Written, not accumulated. */
+ *             grad_weight3[p] (C, C) = grad_y3[p]^T . x; grad_bias3[p] (C) = column sums (array or entries may be NULL).  Written, not accumulated.
+ *   Plain stores only (no atomics, no pre-zeroed outputs), bit-identical from call to call, no allocation or synchronisation inside: capturable.
+ *   Alignment: x, the grad_y3[p] and (wide widths) the weight3[p] must be 16-byte aligned with contiguous rows — rows are read 16 bytes at a time, which
+ *   C % 4 == 0 gives every row of a contiguous tensor whose base is aligned; CBL_ERR_BAD_ARG otherwise.
+ *   workspace (backward): cbl_triple_linear_workspace_bytes(C) bytes, independent of rows — C = 32: 3.2 MB, 64: 12.8 MB (256 row-chunk partials per projection);
+ *   C = 128: 12.7 MB, 256: 25.3 MB, 512: 25.2 MB (at most 64 / 32 / 8 row chunks of >= 128 rows; with one chunk — up to 128 rows, 256 at C = 512 — no workspace
+ *   byte is touched and the weight gradient is one launch, otherwise a pass and a combine).  A smaller workspace_bytes: CBL_ERR_WORKSPACE. */
 size_t cbl_triple_linear_workspace_bytes(int C);
 int cbl_triple_linear_forward(long long rows, int C, const float* x, const float* const* weight3, const float* const* bias3, float* const* y3, void* stream);
 int cbl_triple_linear_backward(long long rows, int C, const float* x, const float* const* weight3, const float* const* grad_y3, float* grad_x,
