@@ -774,7 +774,8 @@ __global__ __launch_bounds__(C) void attn_w2_bwd_reduce_wide_kernel(int n, int K
     if (c < G) mine[2 * C + G * C + c] = dba;
 }
 
-template <int C, int G>
+// SCATTER = false: d x_k is not added here (gathered by attn_w2_gxk_csr_wide_kernel; gxk is not read and may be NULL)
+template <int C, int G, bool SCATTER = true>
 __global__ __launch_bounds__(C) void attn_w2_bwd_apply_wide_kernel(int n, int K, const float* __restrict__ xq, const float* __restrict__ xk,
                                                                    const int* __restrict__ idx, const float* __restrict__ p1,
                                                                    const float* __restrict__ W3C, const float* __restrict__ b3C,
@@ -816,7 +817,7 @@ __global__ __launch_bounds__(C) void attn_w2_bwd_apply_wide_kernel(int n, int K,
                 const float dy = y > 0.f ? dw1 : 0.f;
                 float dw = q.gamma * q.invstd * ((dy - c0) - xh * c1);       // BatchNorm backward, train mode
                 if (k0 + u >= K) dw = 0.f;
-                else unsafeAtomicAdd(gxk + (size_t)jj[u] * C + c, dw);        // w = p_r - x_q + x_k[j]
+                else if (SCATTER) unsafeAtomicAdd(gxk + (size_t)jj[u] * C + c, dw);        // w = p_r - x_q + x_k[j]
                 gq -= dw;
                 d0 += dw * a0; d1 += dw * a1; d2 += dw * a2; db += dw;
                 V[u * wide_stride<C>() + c] = dw;
@@ -859,7 +860,8 @@ __global__ __launch_bounds__(C) void attn_agg_forward_wide_kernel(int n, int K, 
     }
 }
 
-template <int C, int G>
+// SCATTER = false: d x_v is not added here (gathered by attn_agg_gxv_csr_wide_kernel; gxv is not read and may be NULL)
+template <int C, int G, bool SCATTER = true>
 __global__ __launch_bounds__(C) void attn_agg_backward_wide_kernel(int n, int K, const float* __restrict__ xv, const int* __restrict__ idx,
                                                                    const float* __restrict__ p1, const float* __restrict__ W3C, const float* __restrict__ b3C,
                                                                    const float* __restrict__ a, const float* __restrict__ go,
@@ -886,7 +888,7 @@ __global__ __launch_bounds__(C) void attn_agg_backward_wide_kernel(int n, int K,
                 const float a0 = p1[3 * r], a1 = p1[3 * r + 1], a2 = p1[3 * r + 2];
                 float dpe = g * a[r * G + (c % G)];                          // d out / d (x_v[j] + p_r)
                 if (k0 + u >= K) dpe = 0.f;
-                else unsafeAtomicAdd(gxv + (size_t)jj[u] * C + c, dpe);
+                else if (SCATTER) unsafeAtomicAdd(gxv + (size_t)jj[u] * C + c, dpe);
                 d0 += dpe * a0; d1 += dpe * a1; d2 += dpe * a2; db += dpe;
                 V[u * wide_stride<C>() + c] = dpe;
                 DA[u * C + c] = g * (xr[u] + pe_of(q, a0, a1, a2));          // grad_a[i,k,g] = sum over the channels with c % G == g
@@ -917,6 +919,85 @@ __global__ __launch_bounds__(C) void attn_agg_backward_wide_kernel(int n, int K,
     }
     float* mine = partial + (size_t)blockIdx.x * (4 * C);
     mine[3 * c] = d0; mine[3 * c + 1] = d1; mine[3 * c + 2] = d2; mine[3 * C + c] = db;
+}
+
+// the two scatters of the wide passes as gathers: the wide counterparts of attn_agg_gxv_csr_kernel / attn_w2_gxk_csr_kernel (same table, same contract: plain
+// stores, a row nobody lists gets 0, no zero fill, no atomics).  One workgroup of C lanes per target row (lane = channel), grid-stride over the rows: the pair p,
+// its point i = p / K, p1[3p..] and grad_w2[p, :] are uniform across the workgroup (scalar loads), only x_q[i] / grad_out[i] and a's column are per lane.
+// A row's pairs are summed in ascending e by one lane each: the result does not depend on the grid.  The inv_src entries and the per-lane rows of WU pairs are
+// in flight together (the lists are short — K on average — and every step is a dependent load: list entry -> row); hubs are walked by their one workgroup.
+constexpr int WU = 4;
+
+template <int C, int G>
+__global__ __launch_bounds__(C) void attn_agg_gxv_csr_wide_kernel(int n, CblFastDiv dvK, const float* __restrict__ a, const float* __restrict__ go,
+                                                                  const int* __restrict__ order, const int* __restrict__ inv_start, const int* __restrict__ inv_src,
+                                                                  float* __restrict__ gxv)
+{
+    const int c = threadIdx.x;
+    for (int tr = blockIdx.x; tr < n; tr += gridDim.x) {
+        const int j = order ? order[tr] : tr;
+        const int e0 = inv_start[tr], e1 = inv_start[tr + 1];
+        float acc = 0.f;
+        for (int eb = e0; eb < e1; eb += WU) {
+            int p[WU]; float av[WU], gv[WU];
+#pragma unroll
+            for (int u = 0; u < WU; u++) p[u] = inv_src[min(eb + u, e1 - 1)];
+#pragma unroll
+            for (int u = 0; u < WU; u++) { av[u] = a[(size_t)p[u] * G + (c % G)]; gv[u] = go[(size_t)cbl_fastdiv((unsigned)p[u], dvK) * C + c]; }
+#pragma unroll
+            for (int u = 0; u < WU; u++)
+                if (eb + u < e1) acc += gv[u] * av[u];
+        }
+        gxv[(size_t)j * C + c] = acc;
+    }
+}
+
+template <int C, int G>
+__global__ __launch_bounds__(C) void attn_w2_gxk_csr_wide_kernel(int n, int K, CblFastDiv dvK, const float* __restrict__ xq, const float* __restrict__ xk,
+                                                                 const float* __restrict__ p1, const float* __restrict__ W3C, const float* __restrict__ b3C,
+                                                                 const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                 const float* __restrict__ Wa, const float* __restrict__ gw2, const float* __restrict__ sums,
+                                                                 const int* __restrict__ order, const int* __restrict__ inv_start, const int* __restrict__ inv_src,
+                                                                 float* __restrict__ gxk)
+{
+    const int c = threadIdx.x;
+    PairParams q; q.w0 = W3C[3 * c]; q.w1 = W3C[3 * c + 1]; q.w2 = W3C[3 * c + 2]; q.b = b3C[c];
+    q.mean = mean[c]; q.invstd = invstd[c]; q.gamma = gamma ? gamma[c] : 1.f; q.beta = beta ? beta[c] : 0.f;
+    float wa[G];
+#pragma unroll
+    for (int g = 0; g < G; g++) wa[g] = Wa[g * C + c];
+    const float inv_rows = 1.0f / ((float)n * (float)K);
+    const float c0 = sums[c] * inv_rows, c1 = sums[C + c] * inv_rows;
+    for (int tr = blockIdx.x; tr < n; tr += gridDim.x) {
+        const int j = order ? order[tr] : tr;
+        const int e0 = inv_start[tr], e1 = inv_start[tr + 1];
+        const float xkj = xk[(size_t)j * C + c];
+        float acc = 0.f;
+        for (int eb = e0; eb < e1; eb += WU) {
+            int p[WU]; float xqi[WU];
+#pragma unroll
+            for (int u = 0; u < WU; u++) p[u] = inv_src[min(eb + u, e1 - 1)];
+#pragma unroll
+            for (int u = 0; u < WU; u++) xqi[u] = xq[(size_t)cbl_fastdiv((unsigned)p[u], dvK) * C + c];
+#pragma unroll
+            for (int u = 0; u < WU; u++) {
+                if (eb + u < e1) {                                   // (uniform) the apply pass's arithmetic, operation for operation; grad_w2's row read where it is used: no [WU][G] array
+                    const size_t r = (size_t)p[u];
+                    const float a0 = p1[3 * r], a1 = p1[3 * r + 1], a2 = p1[3 * r + 2];
+                    const float w = pe_of(q, a0, a1, a2) - (xqi[u] - xkj);
+                    const float xh = (w - q.mean) * q.invstd;
+                    const float y = xh * q.gamma + q.beta;
+                    float dw1 = 0.f;
+#pragma unroll
+                    for (int g = 0; g < G; g++) dw1 += wa[g] * gw2[r * G + g];
+                    const float dy = y > 0.f ? dw1 : 0.f;
+                    acc += q.gamma * q.invstd * ((dy - c0) - xh * c1);       // BatchNorm backward, train mode: the apply pass's dw
+                }
+            }
+        }
+        gxk[(size_t)j * C + c] = acc;
+    }
 }
 
 // partial rows per pass: one per workgroup; enough workgroups to fill 256 CUs, few enough that the (2C + GC + G)-float rows stay ~30 MB
@@ -1131,6 +1212,84 @@ CBL_EXPORT int cbl_attn_agg_backward_csr(int n, int K, int C, int G, const float
     const unsigned g = cbl_round_up8((unsigned)cbl_grid_for((long long)n * C, AT_BLOCK, 8192));
     if (C == 32) hipLaunchKernelGGL((attn_agg_gxv_csr_kernel<32, 4>), dim3(g), dim3(AT_BLOCK), 0, st, (unsigned)n, dv, a, grad_out, order, inv_start, inv_src, grad_xv);
     else         hipLaunchKernelGGL((attn_agg_gxv_csr_kernel<64, 8>), dim3(g), dim3(AT_BLOCK), 0, st, (unsigned)n, dv, a, grad_out, order, inv_start, inv_src, grad_xv);
+    return cbl_status();
+}
+
+// wide kernels only (C = 128 / 256 / 512, checked by the caller); KERNEL with its template arguments' tail, e.g. AT_DISPATCH_WIDE(attn_w2_bwd_apply_wide_kernel, (, false), ...)
+#define AT_UNPAREN(...) __VA_ARGS__
+#define AT_DISPATCH_WIDE(KERNEL, TAIL, ...)                                                                                    \
+    do {                                                                                                                          \
+        if (C == 128)      hipLaunchKernelGGL((KERNEL<128, 16 AT_UNPAREN TAIL>), dim3(nb), dim3(128), 0, st, __VA_ARGS__);         \
+        else if (C == 256) hipLaunchKernelGGL((KERNEL<256, 32 AT_UNPAREN TAIL>), dim3(nb), dim3(256), 0, st, __VA_ARGS__);         \
+        else               hipLaunchKernelGGL((KERNEL<512, 64 AT_UNPAREN TAIL>), dim3(nb), dim3(512), 0, st, __VA_ARGS__);         \
+    } while (0)
+
+static inline int at_check_wide(int n, int K, int C, int G)
+{
+    const int rc = at_check(n, K, C, G);
+    if (rc) return rc;
+    return C > 64 ? CBL_OK : CBL_ERR_UNSUPPORTED;
+}
+
+// cbl_attn_w2_backward_csr / cbl_attn_agg_backward_csr for the WIDE stages (C = 128 / 256 / 512, G = C / 8; CBL_ERR_UNSUPPORTED otherwise): the passes of
+// cbl_attn_w2_backward / cbl_attn_agg_backward with the scatter compiled out of the apply / aggregation kernel, then one gather launch over the transposed
+// table — grad_xk / grad_xv WRITTEN (no pre-zeroing), no atomics anywhere, deterministic.  The caller owns every buffer; same workspace as the scatter entries.
+CBL_EXPORT int cbl_attn_w2_backward_wide_csr(int n, int K, int C, int G, const float* x_q, const float* x_k, const int* idx, const float* p1,
+                                             const float* W3C, const float* b3C, const float* bn_weight, const float* bn_bias,
+                                             const float* save_mean, const float* save_invstd, const float* Wa, const float* grad_w2,
+                                             const int* order, const int* inv_start, const int* inv_src,
+                                             float* grad_xq, float* grad_xk, float* grad_p1, float* grad_W3C, float* grad_b3C,
+                                             float* grad_bn_weight, float* grad_bn_bias, float* grad_Wa, float* grad_ba,
+                                             void* workspace, size_t workspace_bytes, void* stream)
+{
+    const int rc = at_check_wide(n, K, C, G);
+    if (rc) return rc;
+    if (n == 0) return CBL_OK;
+    if (!x_q || !x_k || !idx || !p1 || !W3C || !b3C || !save_mean || !save_invstd || !Wa || !grad_w2 || !grad_xq || !grad_xk || !grad_p1 || !grad_W3C ||
+        !grad_b3C || !grad_bn_weight || !grad_bn_bias || !grad_Wa || !grad_ba || !workspace || !inv_start || !inv_src) return CBL_ERR_BAD_ARG;
+    if (workspace_bytes < cbl_attn_workspace_bytes(C, G)) return CBL_ERR_WORKSPACE;
+    hipStream_t st = cbl_stream(stream);
+    const int nb = at_blocks(n, C);
+    const int nv1 = 2 * C + G * C + G, nv2 = 4 * C;
+    float* partial = reinterpret_cast<float*>(workspace);
+    float* sums = partial + (size_t)at_wide_blocks(C) * nv1;
+    AT_DISPATCH(attn_w2_bwd_reduce, n, K, x_q, x_k, idx, p1, W3C, b3C, save_mean, save_invstd, bn_weight, bn_bias, Wa, grad_w2, partial);
+    SumSegments s1; s1.dst[0] = grad_bn_bias; s1.dst[1] = grad_bn_weight; s1.dst[2] = grad_Wa; s1.dst[3] = grad_ba;
+    s1.begin[0] = 0; s1.begin[1] = C; s1.begin[2] = 2 * C; s1.begin[3] = 2 * C + G * C; s1.begin[4] = nv1;
+    hipLaunchKernelGGL(attn_sum_partials_kernel, dim3(cbl_div_up(nv1, 16)), dim3(256), 0, st, nv1, nb, partial, s1, sums);
+    AT_DISPATCH_WIDE(attn_w2_bwd_apply_wide_kernel, (, false), n, K, x_q, x_k, idx, p1, W3C, b3C, save_mean, save_invstd, bn_weight, bn_bias, Wa, grad_w2, sums,
+                     grad_xq, (float*)nullptr, grad_p1, partial);
+    SumSegments s2; s2.dst[0] = grad_W3C; s2.dst[1] = grad_b3C; s2.dst[2] = s2.dst[3] = nullptr;
+    s2.begin[0] = 0; s2.begin[1] = 3 * C; s2.begin[2] = s2.begin[3] = s2.begin[4] = nv2;
+    hipLaunchKernelGGL(attn_sum_partials_kernel, dim3(cbl_div_up(nv2, 16)), dim3(256), 0, st, nv2, nb, partial, s2, (float*)nullptr);
+    const CblFastDiv dv = cbl_fastdiv_make((unsigned)K);
+    AT_DISPATCH_WIDE(attn_w2_gxk_csr_wide_kernel, (), n, K, dv, x_q, x_k, p1, W3C, b3C, save_mean, save_invstd, bn_weight, bn_bias, Wa, grad_w2, (const float*)sums,
+                     order, inv_start, inv_src, grad_xk);
+    return cbl_status();
+}
+
+CBL_EXPORT int cbl_attn_agg_backward_wide_csr(int n, int K, int C, int G, const float* x_v, const int* idx, const float* p1, const float* W3C, const float* b3C,
+                                              const float* a, const float* grad_out, const int* order, const int* inv_start, const int* inv_src,
+                                              float* grad_xv, float* grad_p1, float* grad_W3C, float* grad_b3C, float* grad_a,
+                                              void* workspace, size_t workspace_bytes, int softmax, void* stream)
+{
+    const int rc = at_check_wide(n, K, C, G);
+    if (rc) return rc;
+    if (n == 0) return CBL_OK;
+    if (!x_v || !idx || !p1 || !W3C || !b3C || !a || !grad_out || !grad_xv || !grad_p1 || !grad_W3C || !grad_b3C || !grad_a || !workspace || !inv_start || !inv_src)
+        return CBL_ERR_BAD_ARG;
+    if (workspace_bytes < cbl_attn_workspace_bytes(C, G)) return CBL_ERR_WORKSPACE;
+    hipStream_t st = cbl_stream(stream);
+    const int nb = at_blocks(n, C);
+    const int nv2 = 4 * C;
+    float* partial = reinterpret_cast<float*>(workspace);
+    AT_DISPATCH_WIDE(attn_agg_backward_wide_kernel, (, false), n, K, x_v, idx, p1, W3C, b3C, a, grad_out, (float*)nullptr, grad_p1, grad_a, partial, softmax);
+    SumSegments s2; s2.dst[0] = grad_W3C; s2.dst[1] = grad_b3C; s2.dst[2] = s2.dst[3] = nullptr;
+    s2.begin[0] = 0; s2.begin[1] = 3 * C; s2.begin[2] = s2.begin[3] = s2.begin[4] = nv2;
+    hipLaunchKernelGGL(attn_sum_partials_kernel, dim3(cbl_div_up(nv2, 16)), dim3(256), 0, st, nv2, nb, partial, s2, (float*)nullptr);
+    // (with softmax the kernel above has replaced grad_a by the gradient of the logits; the gather needs the softmax WEIGHTS `a`, which are its input)
+    const CblFastDiv dv = cbl_fastdiv_make((unsigned)K);
+    AT_DISPATCH_WIDE(attn_agg_gxv_csr_wide_kernel, (), n, dv, a, grad_out, order, inv_start, inv_src, grad_xv);
     return cbl_status();
 }
 

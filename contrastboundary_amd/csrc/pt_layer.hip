@@ -1566,15 +1566,19 @@ CBL_EXPORT int cbl_pt_layer_wide_forward(int n, int K, int C, const float* xyz, 
     return cbl_status();
 }
 
-CBL_EXPORT int cbl_pt_layer_wide_backward(int n, int K, int C, const float* x_q, const float* x_k, const float* x_v, const int* idx, const float* gamma_p,
-                                          const float* W3C, const float* b3C, const float* gamma_c, const float* beta_c, const float* Wa, const float* gamma_g,
-                                          const float* Wb, const float* p_r, const float* p0, const float* p1, const float* w2, const float* a, const float* consts,
-                                          const float* bnc_stats, const float* grad_out, float* g_xq, float* g_xk, float* g_xv, float* g_Wp, float* g_bp,
-                                          float* g_gamma_p, float* g_beta_p, float* g_W3C, float* g_b3C, float* g_gamma_c, float* g_beta_c, float* g_Wa, float* g_ba,
-                                          float* g_gamma_g, float* g_beta_g, float* g_Wb, float* g_bb, void* workspace, size_t workspace_bytes, void* stream)
+// the wide backward in its two flavours: csr = false scatters d x_k / d x_v with float atomics into targets zeroed here (cbl_pt_layer_wide_backward),
+// csr = true gathers them over the transposed table (cbl_pt_layer_wide_backward_csr: no fill, no atomics); every other launch is the same, in the same order
+static int pw_backward(bool csr, int n, int K, int C, const float* x_q, const float* x_k, const float* x_v, const int* idx,
+                       const int* order, const int* inv_start, const int* inv_src, const float* gamma_p,
+                       const float* W3C, const float* b3C, const float* gamma_c, const float* beta_c, const float* Wa, const float* gamma_g,
+                       const float* Wb, const float* p_r, const float* p0, const float* p1, const float* w2, const float* a, const float* consts,
+                       const float* bnc_stats, const float* grad_out, float* g_xq, float* g_xk, float* g_xv, float* g_Wp, float* g_bp,
+                       float* g_gamma_p, float* g_beta_p, float* g_W3C, float* g_b3C, float* g_gamma_c, float* g_beta_c, float* g_Wa, float* g_ba,
+                       float* g_gamma_g, float* g_beta_g, float* g_Wb, float* g_bb, void* workspace, size_t workspace_bytes, void* stream)
 {
     if (!pw_shape_ok(n, K, C)) return CBL_ERR_UNSUPPORTED;
     if (!consts || !bnc_stats || !workspace || !grad_out) return CBL_ERR_BAD_ARG;
+    if (csr && (!inv_start || !inv_src)) return CBL_ERR_BAD_ARG;
     if (workspace_bytes < cbl_pt_layer_wide_workspace_bytes(n, K, C)) return CBL_ERR_WORKSPACE;
     const PwWs ws = pw_workspace(static_cast<char*>(workspace), n, K, C);
     hipStream_t st = cbl_stream(stream);
@@ -1584,14 +1588,18 @@ CBL_EXPORT int cbl_pt_layer_wide_backward(int n, int K, int C, const float* x_q,
     int rc;
     // the two scatters (d x_k, d x_v) of the wide kernels are float atomics: zero their targets
     const long long nc = (long long)n * C;
-    if (g_xv == g_xk + (size_t)n * C) {                             // one buffer (the Python mirror allocates them together): one fill
+    if (csr) {                                                      // gathered below: written, nothing to zero
+    } else if (g_xv == g_xk + (size_t)n * C) {                      // one buffer (the Python mirror allocates them together): one fill
         hipLaunchKernelGGL(pw_zero_kernel, dim3(cbl_grid_for(2 * nc, 256, 2048)), dim3(256), 0, st, 2 * nc, g_xk);
     } else {
         hipLaunchKernelGGL(pw_zero_kernel, dim3(cbl_grid_for(nc, 256, 2048)), dim3(256), 0, st, nc, g_xk);
         hipLaunchKernelGGL(pw_zero_kernel, dim3(cbl_grid_for(nc, 256, 2048)), dim3(256), 0, st, nc, g_xv);
     }
     // aggregation backward with the softmax backward inside: d x_v, its share of d p1 / d W3C / d b3C, d logits
-    if ((rc = cbl_attn_agg_softmax_backward(n, K, C, G, x_v, idx, p1, W3C, b3C, a, grad_out, g_xv, ws.gp1a, ws.w3c2, ws.b3c2, ws.glogit, ws.attn, ws.attn_bytes, stream))) return rc;
+    if (csr) rc = cbl_attn_agg_backward_wide_csr(n, K, C, G, x_v, idx, p1, W3C, b3C, a, grad_out, order, inv_start, inv_src, g_xv, ws.gp1a, ws.w3c2, ws.b3c2, ws.glogit,
+                                                 ws.attn, ws.attn_bytes, 1, stream);
+    else rc = cbl_attn_agg_softmax_backward(n, K, C, G, x_v, idx, p1, W3C, b3C, a, grad_out, g_xv, ws.gp1a, ws.w3c2, ws.b3c2, ws.glogit, ws.attn, ws.attn_bytes, stream);
+    if (rc) return rc;
     // Linear(G, G), ReLU, BN_g backward
     const long long nbatch = (np + 256 / G - 1) / (256 / G);        // a workgroup takes whole batches of 256 / G pairs
     const unsigned gn = (unsigned)(nbatch < PW_NROWS ? (nbatch > 0 ? nbatch : 1) : PW_NROWS);
@@ -1601,8 +1609,11 @@ CBL_EXPORT int cbl_pt_layer_wide_backward(int n, int K, int C, const float* x_q,
                        ws.bc_g, 64, g_gamma_g, g_beta_g, consts + PW_FS_G, ws.gba2);
     hipLaunchKernelGGL(pw_bn_apply_kernel, dim3(cbl_grid_for(np * G, 256, 1024)), dim3(256), 0, st, np * G, G, ws.pre, w2, ws.bc_g, ws.gw2);
     // the C-wide backward: d x_q, d x_k, its share of d p1 / d W3C / d b3C, BN_c's and Wa's gradients
-    if ((rc = cbl_attn_w2_backward(n, K, C, G, x_q, x_k, idx, p1, W3C, b3C, gamma_c, beta_c, bnc_stats, bnc_stats + C, Wa, ws.gw2, g_xq, g_xk, ws.gp1b,
-                                   ws.w3c2 + 3 * (size_t)C, ws.b3c2 + C, g_gamma_c, g_beta_c, g_Wa, g_ba, ws.attn, ws.attn_bytes, stream))) return rc;
+    if (csr) rc = cbl_attn_w2_backward_wide_csr(n, K, C, G, x_q, x_k, idx, p1, W3C, b3C, gamma_c, beta_c, bnc_stats, bnc_stats + C, Wa, ws.gw2, order, inv_start, inv_src,
+                                                g_xq, g_xk, ws.gp1b, ws.w3c2 + 3 * (size_t)C, ws.b3c2 + C, g_gamma_c, g_beta_c, g_Wa, g_ba, ws.attn, ws.attn_bytes, stream);
+    else rc = cbl_attn_w2_backward(n, K, C, G, x_q, x_k, idx, p1, W3C, b3C, gamma_c, beta_c, bnc_stats, bnc_stats + C, Wa, ws.gw2, g_xq, g_xk, ws.gp1b,
+                                   ws.w3c2 + 3 * (size_t)C, ws.b3c2 + C, g_gamma_c, g_beta_c, g_Wa, g_ba, ws.attn, ws.attn_bytes, stream);
+    if (rc) return rc;
     // p chain backward over the sum of the two d p1
     hipLaunchKernelGGL(pt_pchain_bwd_kernel, dim3(gp), dim3(PT_NARROW_BLOCK), 0, st, np, p_r, p0, p1, ws.gp1a, consts, ws.part_d, (const float*)ws.gp1b);
     hipLaunchKernelGGL(pt_pchain_epilogue_kernel, dim3(1), dim3(PT_FIN_THREADS), 0, st, (int)gp, ws.part_d, np, consts, gamma_p, g_Wp, g_bp, g_gamma_p, g_beta_p);
@@ -1616,5 +1627,32 @@ CBL_EXPORT int cbl_pt_layer_wide_backward(int n, int K, int C, const float* x_q,
     for (int q = 0; q < segs.n; q++) nblk += (unsigned)((segs.s[q].count + 15) / 16);
     hipLaunchKernelGGL(pt_sum_rows_kernel, dim3(nblk), dim3(PT_FIN_THREADS), 0, st, segs);
     return cbl_status();
+}
+
+CBL_EXPORT int cbl_pt_layer_wide_backward(int n, int K, int C, const float* x_q, const float* x_k, const float* x_v, const int* idx, const float* gamma_p,
+                                          const float* W3C, const float* b3C, const float* gamma_c, const float* beta_c, const float* Wa, const float* gamma_g,
+                                          const float* Wb, const float* p_r, const float* p0, const float* p1, const float* w2, const float* a, const float* consts,
+                                          const float* bnc_stats, const float* grad_out, float* g_xq, float* g_xk, float* g_xv, float* g_Wp, float* g_bp,
+                                          float* g_gamma_p, float* g_beta_p, float* g_W3C, float* g_b3C, float* g_gamma_c, float* g_beta_c, float* g_Wa, float* g_ba,
+                                          float* g_gamma_g, float* g_beta_g, float* g_Wb, float* g_bb, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return pw_backward(false, n, K, C, x_q, x_k, x_v, idx, nullptr, nullptr, nullptr, gamma_p, W3C, b3C, gamma_c, beta_c, Wa, gamma_g, Wb, p_r, p0, p1, w2, a, consts,
+                       bnc_stats, grad_out, g_xq, g_xk, g_xv, g_Wp, g_bp, g_gamma_p, g_beta_p, g_W3C, g_b3C, g_gamma_c, g_beta_c, g_Wa, g_ba, g_gamma_g, g_beta_g, g_Wb, g_bb,
+                       workspace, workspace_bytes, stream);
+}
+
+// the same with d x_k / d x_v gathered over the transposed table of idx (cbl_neighbor_transpose with n targets; order may be NULL): g_xk / g_xv are fully WRITTEN,
+// no zero fill, no float atomic in the whole call — run-to-run deterministic.  Same workspace (cbl_pt_layer_wide_workspace_bytes), same saved tensors.
+CBL_EXPORT int cbl_pt_layer_wide_backward_csr(int n, int K, int C, const float* x_q, const float* x_k, const float* x_v, const int* idx,
+                                              const int* order, const int* inv_start, const int* inv_src, const float* gamma_p,
+                                              const float* W3C, const float* b3C, const float* gamma_c, const float* beta_c, const float* Wa, const float* gamma_g,
+                                              const float* Wb, const float* p_r, const float* p0, const float* p1, const float* w2, const float* a, const float* consts,
+                                              const float* bnc_stats, const float* grad_out, float* g_xq, float* g_xk, float* g_xv, float* g_Wp, float* g_bp,
+                                              float* g_gamma_p, float* g_beta_p, float* g_W3C, float* g_b3C, float* g_gamma_c, float* g_beta_c, float* g_Wa, float* g_ba,
+                                              float* g_gamma_g, float* g_beta_g, float* g_Wb, float* g_bb, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return pw_backward(true, n, K, C, x_q, x_k, x_v, idx, order, inv_start, inv_src, gamma_p, W3C, b3C, gamma_c, beta_c, Wa, gamma_g, Wb, p_r, p0, p1, w2, a, consts,
+                       bnc_stats, grad_out, g_xq, g_xk, g_xv, g_Wp, g_bp, g_gamma_p, g_beta_p, g_W3C, g_b3C, g_gamma_c, g_beta_c, g_Wa, g_ba, g_gamma_g, g_beta_g, g_Wb, g_bb,
+                       workspace, workspace_bytes, stream);
 }
 #endif  // CBL_HOST_WAVE_EMULATION

@@ -1,7 +1,7 @@
 #include "cbl_common.h"
 #include <string.h>
 
-CBL_EXPORT const char* cbl_version(void) { return "cbl_amd 0.1 gfx950 (hipcc, -ffp-contract=off)"; }
+CBL_EXPORT const char* cbl_version(void) { return "cbl_amd 0.2 gfx950 (hipcc, -ffp-contract=off)"; }
 
 CBL_EXPORT int cbl_device_arch_ok(void)
 {

@@ -51,7 +51,7 @@ class _KPConv(Function):
         tr = None
         if C % 4 == 0:
             # gather over the transposed neighbour table (no atomics); built where that pays, taken where it already exists
-            tr = pointops.neighbor_transpose(idx, n0, build=(n * K >= pointops.TRANSPOSE_MIN_PAIRS))
+            tr = pointops.neighbor_transpose(idx, n0, build=pointops._build_table(n * K))
         if tr is not None:
             order, inv_start, inv_src = tr
             gf = torch.empty_like(f) if ctx.needs_input_grad[3] else None
@@ -119,7 +119,7 @@ class _AdaptiveWeight(Function):
         tr = None
         if C % 4 == 0:
             # gather over the transposed neighbour table (no atomics, deterministic); built where that pays, taken where it already exists
-            tr = pointops.neighbor_transpose(idx, n0, build=(n * K >= pointops.TRANSPOSE_MIN_PAIRS))
+            tr = pointops.neighbor_transpose(idx, n0, build=pointops._build_table(n * K))
         if tr is not None:
             order, inv_start, inv_src = tr
             gf = torch.empty_like(f) if need_f else None
@@ -186,7 +186,7 @@ class _PosPool(Function):
         if red != 2 and C % 4 == 0:
             # 'sum' / 'mean': a gather over the transposed neighbour table (no atomics, deterministic), built where that pays, taken where it exists
             from . import pointops
-            tr = pointops.neighbor_transpose(idx, n0, build=(n * K >= pointops.TRANSPOSE_MIN_PAIRS))
+            tr = pointops.neighbor_transpose(idx, n0, build=pointops._build_table(n * K))
             if tr is not None:
                 order, inv_start, inv_src = tr
                 gf = torch.empty_like(f)

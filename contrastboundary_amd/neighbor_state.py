@@ -158,6 +158,45 @@ class natural_order:
         return False
 
 
+# ------------------------------------------------------------------------------------------------ deterministic training mode
+_deterministic = False
+
+
+def set_deterministic(on):
+    """Process-global switch (not thread-local: backward passes run on autograd's thread), default off.  On: no backward pass of the library's training path
+    adds with float atomics — the wide attention stages (pt_layer.PTAttentionWide / PTAttentionWideProjected, attention.AttnW2 / AttnAgg at C > 64) gather
+    d x_k / d x_v over the transposed neighbour table (cbl_pt_layer_wide_backward_csr, cbl_attn_*_backward_wide_csr), and every generic operator that
+    builds the table only from pointops.TRANSPOSE_MIN_PAIRS pairs up (grouping / queryandgroup, interpolation, subtraction, aggregation, the local-aggregation
+    operators) builds it always (pointops._build_table).  Two runs of a step from the same state then give the same BITS; the values differ from the
+    default path's in the last bits (another summation order), so this is not a measurement knob.  Forward passes and the default routing are untouched.
+    Where a table cannot be built (more than 2^20 target rows: cbl_neighbor_transpose answers CBL_ERR_UNSUPPORTED) the generic operators keep their
+    atomic kernels; the wide layers raise instead.  Returns the previous setting."""
+    global _deterministic
+    was = _deterministic
+    _deterministic = bool(on)
+    return was
+
+
+def is_deterministic():
+    return _deterministic
+
+
+class deterministic:
+    """inside: `set_deterministic(True)` (or the given value); the previous setting comes back on exit.  A hipGraph captured inside (train_step.GraphedTrainStep,
+    torch.cuda.graph) holds the deterministic kernels and replays them wherever the switch stands later."""
+
+    def __init__(self, on=True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.was = set_deterministic(self.on)
+        return self
+
+    def __exit__(self, *exc):
+        set_deterministic(self.was)
+        return False
+
+
 # ------------------------------------------------------------------------------------------------ transposed neighbour tables
 # cbl_neighbor_transpose of a neighbour table, kept per table.  A module-level registry (not the thread-local cache): backward passes run on
 # autograd's device thread and must find what the forward thread built.  Unlike a processing order the VALUES of a consumer depend on

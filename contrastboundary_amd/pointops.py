@@ -293,6 +293,13 @@ def knn_block_candidates(nsample, xyz, offset, algo="set"):
 TRANSPOSE_MIN_PAIRS = 1 << 16      # below this a scatter with atomics is as quick as building the table (unless the table is cached)
 
 
+def _build_table(pairs):
+    """should a backward pass over `pairs` (source, neighbour) pairs BUILD the transposed table when none is registered?  Where that pays — and always in the
+    deterministic mode (neighbor_state.set_deterministic), which trades the small stages' quicker atomic scatters for fixed summation orders.  A table that
+    cannot be built (more than 2^20 target rows) still leaves the caller its atomic kernel, in either mode."""
+    return neighbor_state.is_deterministic() or pairs >= TRANSPOSE_MIN_PAIRS
+
+
 def neighbor_transpose(idx, n, build=True, companion=None):
     """Transposed neighbour table of idx (m, nsample) over n target rows (cbl_neighbor_transpose, SURVEY.md 7 hard part 6):
     -> (order or None, inv_start (n+1) i32, inv_src (m*nsample) i32), or None (build=False and nothing cached).
@@ -343,7 +350,7 @@ def _scatter_rows(grad_rows, idx, n, col0=0, c=None):
     m, nsample, width = grad_rows.shape
     c = width - col0 if c is None else c
     L = _lib.lib()
-    tr = neighbor_transpose(idx, n, build=(m * nsample >= TRANSPOSE_MIN_PAIRS))
+    tr = neighbor_transpose(idx, n, build=_build_table(m * nsample))
     if tr is not None:
         order, inv_start, inv_src = tr
         grad_in = torch.empty((n, c), dtype=torch.float32, device=grad_rows.device)
@@ -480,7 +487,7 @@ class Subtraction(Function):
         grad_output = grad_output.contiguous()
         n, nsample, c = grad_output.shape
         g1 = torch.zeros((n, c), dtype=torch.float32, device=grad_output.device)
-        tr = neighbor_transpose(idx, ctx.n2, build=(n * nsample >= TRANSPOSE_MIN_PAIRS))
+        tr = neighbor_transpose(idx, ctx.n2, build=_build_table(n * nsample))
         if tr is not None:                                           # K8 as a gather over the transposed table: no atomics (cbl_amd.h)
             order, inv_start, inv_src = tr
             g2 = torch.empty((ctx.n2, c), dtype=torch.float32, device=grad_output.device)
@@ -522,7 +529,7 @@ class Aggregation(Function):
         dev = grad_output.device
         gp = torch.zeros((n, nsample, c), dtype=torch.float32, device=dev)
         gw = torch.zeros((n, nsample, w_c), dtype=torch.float32, device=dev)
-        tr = neighbor_transpose(idx, input.shape[0], build=(n * nsample >= TRANSPOSE_MIN_PAIRS))
+        tr = neighbor_transpose(idx, input.shape[0], build=_build_table(n * nsample))
         if tr is not None:                                           # grad_input of K10 as a gather over the transposed table, the per-pair outputs as before
             order, inv_start, inv_src = tr
             L = _lib.lib()
@@ -574,7 +581,7 @@ class Interpolation(Function):
         idx, weight = ctx.saved_tensors
         grad_output = grad_output.contiguous()
         n, c = grad_output.shape
-        tr = neighbor_transpose(idx, ctx.m, build=(n * ctx.k >= TRANSPOSE_MIN_PAIRS))
+        tr = neighbor_transpose(idx, ctx.m, build=_build_table(n * ctx.k))
         if tr is not None:                                           # K6 as a gather over the transposed table: no atomics (cbl_amd.h)
             order, inv_start, inv_src = tr
             grad_input = torch.empty((ctx.m, c), dtype=torch.float32, device=grad_output.device)
@@ -613,6 +620,14 @@ class WeightedGather(Function):
         idx, weight = ctx.saved_tensors
         grad_output = grad_output.contiguous()
         n, c = grad_output.shape
+        tr = neighbor_transpose(idx, ctx.m, build=True) if neighbor_state.is_deterministic() else None
+        if tr is not None:                                           # deterministic mode: K6 as a gather, as Interpolation.backward
+            order, inv_start, inv_src = tr
+            grad_input = torch.empty((ctx.m, c), dtype=torch.float32, device=grad_output.device)
+            _lib.check(_lib.lib().cbl_weighted_scatter_csr(_c_int(ctx.m), _c_int(ctx.k), _c_int(c), _c_int(1), _lib.ptr(grad_output), _lib.ptr(weight),
+                                                           _lib.ptr(order), _lib.ptr(inv_start), _lib.ptr(inv_src), _lib.ptr(grad_input),
+                                                           _lib.stream_of(grad_output)), "cbl_weighted_scatter_csr")
+            return grad_input, None, None
         grad_input = torch.zeros((ctx.m, c), dtype=torch.float32, device=grad_output.device)
         _lib.check(_lib.lib().cbl_interpolation_backward(_c_int(n), _c_int(c), _c_int(ctx.k), _lib.ptr(grad_output), _lib.ptr(idx),
                                                          _lib.ptr(weight), _lib.ptr(grad_input), _lib.stream_of(grad_output)),

@@ -273,6 +273,8 @@ class GraphedTrainStep:
     40960-point scene in round 5, 17 ms when this was written) takes as long as the step itself (10.7 ms): with a single batch in flight the step
     waits for it (round 5, `--depth 1`: 13.3 ms per step, 3.7 ms of it idle); two chains side by side deliver a batch every 5.5 ms.  All batches must
     have the first batch's shapes (fixed points per scene, as the reference's voxel_max crop gives).
+    The deterministic training mode (neighbor_state.set_deterministic) is read while the graphs are captured, i.e. in the constructor: a step built under the
+    switch replays the deterministic (gather) kernels whatever the switch says later, one built without it replays the atomics.
 
         step = GraphedTrainStep(model, criterion, optimizer, first_inputs, first_target)
         step.stage(batch0); step.stage(batch1)                  # `depth` batches ahead

@@ -4,7 +4,11 @@ aggregation — as ONE autograd Function over the layer's own parameter tensors,
 share_planes = 8, K = 8 | 16).  Training mode: five forward and six backward passes over the (point, neighbour) pairs, nothing of shape
 (n, K, C) stored, no atomics (the x_k / x_v gradients are gathers over the transposed neighbour table), run-to-run deterministic.  Evaluation mode
 under torch.no_grad(): cbl_pt_layer_forward_eval (running statistics, no statistics passes).  `supported()` says when; other shapes, and evaluation
-with gradients enabled, take attention.py's kernels."""
+with gradients enabled, take attention.py's kernels.
+The WIDE stages (C = 128 | 256 | 512: PTAttentionWide / PTAttentionWideProjected, cbl_pt_layer_wide_*) add d x_k / d x_v with float atomics by default — their
+tensors are small and the gathers cost about what the atomics save — and are run-to-run deterministic only under `neighbor_state.deterministic()`
+(`contrastboundary_amd.deterministic`), where their backward is cbl_pt_layer_wide_backward_csr: the same kernels with the two scatters as gathers over the
+transposed table."""
 import ctypes
 
 import torch
@@ -146,7 +150,10 @@ def _wide_forward(p, x_q, x_k, x_v, idx, bns, params):
 
 
 def _wide_backward(x_q, x_k, x_v, idx, kept, params, g_out, g_qkv):
-    """cbl_pt_layer_wide_backward; g_qkv (3, n, C) receives d x_q / d x_k / d x_v (the last two adjacent: the call zeroes both scatter targets with one fill)"""
+    """cbl_pt_layer_wide_backward; g_qkv (3, n, C) receives d x_q / d x_k / d x_v (the last two adjacent: the call zeroes both scatter targets with one fill).
+    In the deterministic mode (neighbor_state.set_deterministic): cbl_pt_layer_wide_backward_csr over the transposed table of idx — d x_k / d x_v gathered,
+    no fill, no float atomics; a table that cannot be built is an error, not a way back to the atomics."""
+    from . import neighbor_state
     p_r, p0, p1, w2, a, consts, bnc = kept
     Wp, bp, gamma_p, beta_p, W3C, b3C, gamma_c, beta_c, Wa, ba, gamma_g, beta_g, Wb, bb = params
     n, C = x_q.shape
@@ -154,6 +161,17 @@ def _wide_backward(x_q, x_k, x_v, idx, kept, params, g_out, g_qkv):
     L = _lib.lib()
     g_params = [torch.empty_like(t) for t in params]
     ws = _workspace(L.cbl_pt_layer_wide_workspace_bytes(_i(n), _i(K), _i(C)), x_q.device)
+    if neighbor_state.is_deterministic():
+        from . import pointops
+        tr = pointops.neighbor_transpose(idx, n, build=True)
+        if tr is None:
+            raise _lib.CblError("deterministic pt_layer wide backward needs the transposed neighbour table (n <= %d)" % MAX_POINTS)
+        order, inv_start, inv_src = tr
+        _lib.check(L.cbl_pt_layer_wide_backward_csr(_i(n), _i(K), _i(C), _P(x_q), _P(x_k), _P(x_v), _P(idx), _P(order), _P(inv_start), _P(inv_src), _P(gamma_p),
+                                                    _P(W3C), _P(b3C), _P(gamma_c), _P(beta_c), _P(Wa), _P(gamma_g), _P(Wb), _P(p_r), _P(p0), _P(p1), _P(w2), _P(a),
+                                                    _P(consts), _P(bnc), _P(g_out.contiguous()), _P(g_qkv[0]), _P(g_qkv[1]), _P(g_qkv[2]), *[_P(t) for t in g_params],
+                                                    _P(ws), ctypes.c_size_t(ws.numel()), _lib.stream_of(x_q)), "cbl_pt_layer_wide_backward_csr")
+        return g_params
     _lib.check(L.cbl_pt_layer_wide_backward(_i(n), _i(K), _i(C), _P(x_q), _P(x_k), _P(x_v), _P(idx), _P(gamma_p), _P(W3C), _P(b3C), _P(gamma_c), _P(beta_c),
                                             _P(Wa), _P(gamma_g), _P(Wb), _P(p_r), _P(p0), _P(p1), _P(w2), _P(a), _P(consts), _P(bnc), _P(g_out.contiguous()),
                                             _P(g_qkv[0]), _P(g_qkv[1]), _P(g_qkv[2]), *[_P(t) for t in g_params], _P(ws), ctypes.c_size_t(ws.numel()),

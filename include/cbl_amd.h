@@ -38,7 +38,7 @@ extern "C" {
 #define CBL_CONTRAST_PAIRS_MAX_D 4096   /* widest feature row of cbl_contrast_pairs_* (the TF head's widest stage is 2304) */
 
 /* library / build identification (host only) */
-const char* cbl_version(void);            /* e.g. "cbl_amd 0.1 gfx950" */
+const char* cbl_version(void);            /* e.g. "cbl_amd 0.2 gfx950"; 0.2: + the three *_wide_csr entries */
 int         cbl_device_arch_ok(void);     /* 1 if the current HIP device is gfx950, 0 otherwise, <0 no device */
 
 /* ------------------------------------------------------------------------------------------------
@@ -506,6 +506,22 @@ int cbl_attn_agg_backward_csr(int n, int K, int C, int G, const float* x_v, cons
                               const float* a, const float* grad_out, const int* order, const int* inv_start, const int* inv_src,
                               float* grad_xv, float* grad_p1, float* grad_W3C, float* grad_b3C, float* grad_a,
                               void* workspace, size_t workspace_bytes, int softmax, void* stream);
+/* the same two entries for the WIDE stages (C = 128 | 256 | 512 with G = C / 8; CBL_ERR_UNSUPPORTED otherwise, CBL_ERR_BAD_ARG without a table, n == 0 is CBL_OK):
+ * they replace cbl_attn_w2_backward / cbl_attn_agg_backward (+ cbl_attn_agg_softmax_backward) where a step has to be reproducible bit for bit — the apply /
+ * aggregation kernel runs without its float atomic and one workgroup per target row gathers grad_xk / grad_xv (n, C) over the table: WRITTEN, no pre-zeroing,
+ * summed in ascending pair order whatever the grid.  Argument lists, shapes and workspace (cbl_attn_workspace_bytes) as the two entries above; the caller owns
+ * every buffer. */
+int cbl_attn_w2_backward_wide_csr(int n, int K, int C, int G, const float* x_q, const float* x_k, const int* idx, const float* p1,
+                                  const float* W3C, const float* b3C, const float* bn_weight, const float* bn_bias,
+                                  const float* save_mean, const float* save_invstd, const float* Wa, const float* grad_w2,
+                                  const int* order, const int* inv_start, const int* inv_src,
+                                  float* grad_xq, float* grad_xk, float* grad_p1, float* grad_W3C, float* grad_b3C,
+                                  float* grad_bn_weight, float* grad_bn_bias, float* grad_Wa, float* grad_ba,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+int cbl_attn_agg_backward_wide_csr(int n, int K, int C, int G, const float* x_v, const int* idx, const float* p1, const float* W3C, const float* b3C,
+                                   const float* a, const float* grad_out, const int* order, const int* inv_start, const int* inv_src,
+                                   float* grad_xv, float* grad_p1, float* grad_W3C, float* grad_b3C, float* grad_a,
+                                   void* workspace, size_t workspace_bytes, int softmax, void* stream);
 
 /* a4  PointTransformerLayer  pytorch/model/blocks.py:31-44 as ONE pass structure (round 4): everything of the layer behind its three per-point
  *     Linear layers (blocks.py:33), train-mode BatchNorms, C = 32 | 64 (share_planes 8, G = C/8), K = 8 | 16 (the two full-resolution stages).
@@ -541,6 +557,17 @@ int cbl_pt_layer_wide_backward(int n, int K, int C, const float* x_q, const floa
                                const float* bnc_stats, const float* grad_out, float* g_xq, float* g_xk, float* g_xv, float* g_Wp, float* g_bp,
                                float* g_gamma_p, float* g_beta_p, float* g_W3C, float* g_b3C, float* g_gamma_c, float* g_beta_c, float* g_Wa, float* g_ba,
                                float* g_gamma_g, float* g_beta_g, float* g_Wb, float* g_bb, void* workspace, size_t workspace_bytes, void* stream);
+/* cbl_pt_layer_wide_backward without its float atomics (the deterministic training mode): order (n, or NULL) / inv_start (n + 1) / inv_src (n K) = the transposed
+ * table of idx (cbl_neighbor_transpose, n targets), after idx; every other argument, the saved tensors and the workspace (cbl_pt_layer_wide_workspace_bytes) as
+ * cbl_pt_layer_wide_backward.  g_xk / g_xv (n, C) are fully WRITTEN by gathers (cbl_attn_*_backward_wide_csr): no zero fill, the caller need not lay them out
+ * adjacently; every other output comes from the same kernels in the same order and is bit for bit what cbl_pt_layer_wide_backward gives. */
+int cbl_pt_layer_wide_backward_csr(int n, int K, int C, const float* x_q, const float* x_k, const float* x_v, const int* idx,
+                                   const int* order, const int* inv_start, const int* inv_src, const float* gamma_p,
+                                   const float* W3C, const float* b3C, const float* gamma_c, const float* beta_c, const float* Wa, const float* gamma_g,
+                                   const float* Wb, const float* p_r, const float* p0, const float* p1, const float* w2, const float* a, const float* consts,
+                                   const float* bnc_stats, const float* grad_out, float* g_xq, float* g_xk, float* g_xv, float* g_Wp, float* g_bp,
+                                   float* g_gamma_p, float* g_beta_p, float* g_W3C, float* g_b3C, float* g_gamma_c, float* g_beta_c, float* g_Wa, float* g_ba,
+                                   float* g_gamma_g, float* g_beta_g, float* g_Wb, float* g_bb, void* workspace, size_t workspace_bytes, void* stream);
 
 /* self-test of the numerical assumption the passes' agreeing ReLU masks rest on: one v_mfma_f32_16x16x4_f32 tile D = A (16,4) . B (4,16) + C (16,16)
  * (row-major device arrays) next to the k-ordered fmaf chain of the same tile; callers compare the two outputs bit for bit. */

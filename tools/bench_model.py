@@ -44,6 +44,7 @@ def parse(argv=None):
     ap.add_argument("--hook-reducer", action="store_true", help="data-parallel runs: round 4's layout (every .grad a view of the flat buffer, accumulated in place, per-tensor optimizer) "
                                                                "instead of the flat state (packed gradients, one fused optimizer kernel, one buffer broadcast)")
     ap.add_argument("--no-buffer-broadcast", action="store_true", help="data-parallel graph runs: skip the per-step broadcast of rank 0's buffers (bisecting the wrapper's cost)")
+    ap.add_argument("--deterministic", action="store_true", help="the deterministic training mode (contrastboundary_amd.set_deterministic): no float atomics in any backward pass")
     ap.add_argument("--host-dry-run", action="store_true")
     return ap.parse_args(argv)
 
@@ -111,6 +112,7 @@ def host_dry_run(a, D, world, rank):
 def run(a, D, world, rank, local):
     from contrastboundary_amd import neighbor_state, pointtransformer_seg as M, synthetic as S, train_step
     torch.cuda.set_device(local)
+    neighbor_state.set_deterministic(a.deterministic)                # before anything is captured: a graphed step replays what the switch said at capture
     dist_on = world > 1 or a.single_rank_group
     if world > 1:
         D.init("nccl")
@@ -189,7 +191,7 @@ def run(a, D, world, rank, local):
     out = {"workload": f"PointTransformerSeg+CBL train step, {a.scenes} x S-room({a.n}) per rank", "n_gpus": world, "ranks": timed.ranks, "ms_per_step": dt * 1e3,
            "points_per_s": a.n * a.scenes * world / dt, "scaling": "weak", "scenes_of_rank0": mine,
            "knn_requests": None if nc is None else nc.hits + nc.misses, "knn_searches": None if nc is None else nc.misses,
-           "geometry_prefetch": bool(a.prefetch or a.graph), "hipgraph": bool(a.graph), "blas": a.blas, "segments_ms": segments,
+           "geometry_prefetch": bool(a.prefetch or a.graph), "hipgraph": bool(a.graph), "deterministic": bool(a.deterministic), "blas": a.blas, "segments_ms": segments,
            "grad_allreduce": None if trainer is None else dict(trainer.describe(), mode="behind the graph replay, in bucket order" if a.graph else "from autograd hooks, beside the backward pass"),
            "loss": [round(float(v), 5) for v in loss.detach().cpu()]}
     if rank == 0:

@@ -1,5 +1,6 @@
 """Per-kernel and per-pass timing of the Point-Transformer layer (csrc/pt_layer.hip) at a stage shape, eager, HIP events:
-    python tools/pt_layer_time.py [n K C] [--graph]      -> one JSON line (layer forward / backward: the fused path issued eagerly and as replayed hipGraphs ("graph"), and round 3's split kernels)"""
+    python tools/pt_layer_time.py [n K C] [--graph] [--deterministic]      -> one JSON line (layer forward / backward: the fused path issued eagerly and as replayed hipGraphs ("graph"), and round 3's split kernels)
+--deterministic: under contrastboundary_amd.set_deterministic(True) (the wide stages' d x_k / d x_v as gathers; the table is built once and found by every later call)"""
 import json
 import os
 import sys
@@ -62,6 +63,10 @@ def main():
                 NS._order_registry[NS._order_key(t)] = {cur.cuda_stream: (order, cur)}
         out_order = which[0]
     out = {"n": n, "K": K, "C": C}
+    if "--deterministic" in sys.argv:
+        import contrastboundary_amd
+        contrastboundary_amd.set_deterministic(True)
+        out["deterministic"] = True
     if which:
         out["order"] = out_order
     for mode in ((True, "ops") if C > 64 else (True, "split")):

@@ -1,4 +1,5 @@
-"""run-to-run spread of a 4-step eager training trajectory on the golden 8192-point scene (python tools/traj_determinism.py [fused|split|plain])"""
+"""run-to-run spread of a 4-step eager training trajectory on the golden 8192-point scene (python tools/traj_determinism.py [fused|split|plain] [deterministic]);
+a trailing `deterministic` runs under contrastboundary_amd.set_deterministic(True): expected spread 0"""
 import copy
 import os
 import sys
@@ -10,7 +11,13 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tests.test_gpu_model import build, CASES  # noqa: E402
 from contrastboundary_amd import blocks  # noqa: E402
 
-mode = sys.argv[1] if len(sys.argv) > 1 else "fused"
+args = sys.argv[1:]
+det = bool(args) and args[-1] == "deterministic"
+if det:
+    import contrastboundary_amd
+    contrastboundary_amd.set_deterministic(True)
+    args = args[:-1]
+mode = args[0] if args else "fused"
 M, model, crit, g = build(CASES[0])
 model = model.cuda().train()
 for m in model.modules():
@@ -35,7 +42,7 @@ for r in range(4):
         traj.append(loss.detach().cpu().numpy().astype(np.float64))
     runs.append(np.stack(traj))
 ref = runs[0]
-print("mode", mode)
+print("mode", mode, "deterministic" if det else "")
 for s in range(4):
     dev = max(float(np.max(np.abs(r[s] - ref[s]) / np.maximum(np.abs(ref[s]), 1e-12))) for r in runs[1:])
     print("step %d  loss %s  max relative spread over 3 reruns %.2e" % (s, np.array2string(ref[s], precision=4), dev))
