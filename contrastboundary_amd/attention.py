@@ -1,7 +1,7 @@
 """Fused C-wide part of PointTransformerLayer's vector attention (csrc/attention.hip, /root/reference/pytorch/model/blocks.py:31-44):
-`attn_w2` and `attn_agg` as autograd Functions over the layer's own parameter tensors.  Available for the two full-resolution
-stages (C = 32 / 64 with share_planes = 8, K <= 64) in training mode (the BatchNorm inside is the train-mode one; evaluation takes the
-separate kernels); `supported()` says when."""
+`attn_w2` and `attn_agg` as autograd Functions over the layer's own parameter tensors.  Available for the five stage widths
+(C = 32 / 64 / 128 / 256 / 512 with share_planes = 8, K <= 64; the two full-resolution widths from 16384 pairs up) in training mode (the BatchNorm inside is the
+train-mode one; evaluation takes the separate kernels); `supported()` says when."""
 import ctypes
 
 import torch
@@ -73,23 +73,18 @@ class AttnW2(Function):
         g_W3C, g_b3C, g_bw, g_bb, g_Wa, g_ba = e(C, 3), e(C), e(C), e(C), e(G, C), e(G)
         g_w2 = g_w2.contiguous()
         tr = _table(idx, n, C)
-        if tr is not None:                                          # the x_k scatter as a gather over the transposed table: no atomics
-            order, inv_start, inv_src = tr
-            g_xq, g_xk, g_p1 = e(n, C), e(n, C), e(n, K, 3)
-            fn, what = (L.cbl_attn_w2_backward_wide_csr, "cbl_attn_w2_backward_wide_csr") if C > 64 else (L.cbl_attn_w2_backward_csr, "cbl_attn_w2_backward_csr")
-            _lib.check(fn(_i(n), _i(K), _i(C), _i(G), _lib.ptr(x_q), _lib.ptr(x_k), _lib.ptr(idx), _lib.ptr(p1), _lib.ptr(W3C), _lib.ptr(b3C),
-                                                  _lib.ptr(bn_w), _lib.ptr(bn_b), _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(Wa), _lib.ptr(g_w2),
-                                                  _lib.ptr(order), _lib.ptr(inv_start), _lib.ptr(inv_src),
-                                                  _lib.ptr(g_xq), _lib.ptr(g_xk), _lib.ptr(g_p1), _lib.ptr(g_W3C), _lib.ptr(g_b3C), _lib.ptr(g_bw), _lib.ptr(g_bb),
-                                                  _lib.ptr(g_Wa), _lib.ptr(g_ba), _lib.ptr(ws), ctypes.c_size_t(ws.numel()), _lib.stream_of(x_q)),
-                       what)
-            return g_xq, g_xk, g_p1, g_W3C, g_b3C, g_bw, g_bb, g_Wa, g_ba, None, None, None
-        g_xq, g_xk, g_p1 = e(n, C), torch.zeros(n, C, dtype=torch.float32, device=dev), e(n, K, 3)
-        _lib.check(L.cbl_attn_w2_backward(_i(n), _i(K), _i(C), _i(G), _lib.ptr(x_q), _lib.ptr(x_k), _lib.ptr(idx), _lib.ptr(p1), _lib.ptr(W3C), _lib.ptr(b3C),
-                                          _lib.ptr(bn_w), _lib.ptr(bn_b), _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(Wa), _lib.ptr(g_w2),
-                                          _lib.ptr(g_xq), _lib.ptr(g_xk), _lib.ptr(g_p1), _lib.ptr(g_W3C), _lib.ptr(g_b3C), _lib.ptr(g_bw), _lib.ptr(g_bb),
-                                          _lib.ptr(g_Wa), _lib.ptr(g_ba), _lib.ptr(ws), ctypes.c_size_t(ws.numel()), _lib.stream_of(x_q)),
-                   "cbl_attn_w2_backward")
+        g_xq = e(n, C)
+        if tr is not None:                                          # the x_k scatter as a gather over the transposed table: no atomics, g_xk written
+            what, g_xk = "cbl_attn_w2_backward_wide_csr" if C > 64 else "cbl_attn_w2_backward_csr", e(n, C)
+        else:                                                       # float atomics into zeroed rows
+            what, g_xk = "cbl_attn_w2_backward", torch.zeros(n, C, dtype=torch.float32, device=dev)
+        g_p1 = e(n, K, 3)
+        args = [_i(n), _i(K), _i(C), _i(G), _lib.ptr(x_q), _lib.ptr(x_k), _lib.ptr(idx), _lib.ptr(p1), _lib.ptr(W3C), _lib.ptr(b3C), _lib.ptr(bn_w), _lib.ptr(bn_b),
+                _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(Wa), _lib.ptr(g_w2)]
+        args += [_lib.ptr(t) for t in tr or ()]                     # order, inv_start, inv_src
+        args += [_lib.ptr(g_xq), _lib.ptr(g_xk), _lib.ptr(g_p1), _lib.ptr(g_W3C), _lib.ptr(g_b3C), _lib.ptr(g_bw), _lib.ptr(g_bb), _lib.ptr(g_Wa), _lib.ptr(g_ba),
+                 _lib.ptr(ws), ctypes.c_size_t(ws.numel()), _lib.stream_of(x_q)]
+        _lib.check(getattr(L, what)(*args), what)
         return g_xq, g_xk, g_p1, g_W3C, g_b3C, g_bw, g_bb, g_Wa, g_ba, None, None, None
 
 
@@ -127,18 +122,15 @@ class AttnAgg(Function):
         e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         g_out = g_out.contiguous()
         tr = _table(idx, n, C)
-        if tr is not None:                                          # the x_v scatter as a gather over the transposed table: no atomics
-            order, inv_start, inv_src = tr
-            g_xv, g_p1, g_W3C, g_b3C, g_a = e(n, C), e(n, K, 3), e(C, 3), e(C), e(n, K, G)
-            fn, what = (L.cbl_attn_agg_backward_wide_csr, "cbl_attn_agg_backward_wide_csr") if C > 64 else (L.cbl_attn_agg_backward_csr, "cbl_attn_agg_backward_csr")
-            _lib.check(fn(_i(n), _i(K), _i(C), _i(G), _lib.ptr(x_v), _lib.ptr(idx), _lib.ptr(p1), _lib.ptr(W3C), _lib.ptr(b3C), _lib.ptr(a),
-                                                   _lib.ptr(g_out), _lib.ptr(order), _lib.ptr(inv_start), _lib.ptr(inv_src), _lib.ptr(g_xv), _lib.ptr(g_p1),
-                                                   _lib.ptr(g_W3C), _lib.ptr(g_b3C), _lib.ptr(g_a), _lib.ptr(ws), ctypes.c_size_t(ws.numel()),
-                                                   _i(1 if ctx.softmax else 0), _lib.stream_of(x_v)), what)
-            return g_xv, g_p1, g_W3C, g_b3C, g_a, None, None
-        g_xv, g_p1, g_W3C, g_b3C, g_a = torch.zeros(n, C, dtype=torch.float32, device=dev), e(n, K, 3), e(C, 3), e(C), e(n, K, G)
-        fn, what = (L.cbl_attn_agg_softmax_backward, "cbl_attn_agg_softmax_backward") if ctx.softmax else (L.cbl_attn_agg_backward, "cbl_attn_agg_backward")
-        _lib.check(fn(_i(n), _i(K), _i(C), _i(G), _lib.ptr(x_v), _lib.ptr(idx), _lib.ptr(p1), _lib.ptr(W3C), _lib.ptr(b3C), _lib.ptr(a),
-                      _lib.ptr(g_out), _lib.ptr(g_xv), _lib.ptr(g_p1), _lib.ptr(g_W3C), _lib.ptr(g_b3C), _lib.ptr(g_a), _lib.ptr(ws),
-                      ctypes.c_size_t(ws.numel()), _lib.stream_of(x_v)), what)
+        if tr is not None:                                          # the x_v scatter as a gather over the transposed table: no atomics, g_xv written
+            what, g_xv = "cbl_attn_agg_backward_wide_csr" if C > 64 else "cbl_attn_agg_backward_csr", e(n, C)
+        else:                                                       # float atomics into zeroed rows
+            what, g_xv = "cbl_attn_agg_softmax_backward" if ctx.softmax else "cbl_attn_agg_backward", torch.zeros(n, C, dtype=torch.float32, device=dev)
+        g_p1, g_W3C, g_b3C, g_a = e(n, K, 3), e(C, 3), e(C), e(n, K, G)
+        args = [_i(n), _i(K), _i(C), _i(G), _lib.ptr(x_v), _lib.ptr(idx), _lib.ptr(p1), _lib.ptr(W3C), _lib.ptr(b3C), _lib.ptr(a), _lib.ptr(g_out)]
+        args += [_lib.ptr(t) for t in tr or ()]                     # order, inv_start, inv_src
+        args += [_lib.ptr(g_xv), _lib.ptr(g_p1), _lib.ptr(g_W3C), _lib.ptr(g_b3C), _lib.ptr(g_a), _lib.ptr(ws), ctypes.c_size_t(ws.numel())]
+        if tr is not None:
+            args.append(_i(1 if ctx.softmax else 0))                # the scatter entries carry the softmax in their name, the gather entries as a flag
+        _lib.check(getattr(L, what)(*args, _lib.stream_of(x_v)), what)
         return g_xv, g_p1, g_W3C, g_b3C, g_a, None, None

@@ -1004,17 +1004,47 @@ __global__ __launch_bounds__(C) void attn_w2_gxk_csr_wide_kernel(int n, int K, C
 // (C = 128: 2048 since round 5 — with several scenes per step the stage has 10^4 points and more, and the passes are latency chains per point: twice the workgroups
 //  in flight took the layer from 1400 to 1214 us at 20480 points, 729 to 654 at 10240; four times measured no better; one scene has 2560 points = 2560 workgroups either way)
 constexpr int at_wide_blocks(int C) { return C <= 128 ? 2048 : (C <= 256 ? 768 : 256); }
+constexpr int at_max_rows(int C) { return C > 64 ? at_wide_blocks(C) : AT_MAX_BLOCKS; }
 
-int at_check(int n, int K, int C, int G)
+// shape, then the widths: the five the kernels exist for, of which an entry may refuse some (`width_ok` false)
+int at_check(int n, int K, int C, int G, bool width_ok = true)
 {
     if (n < 0 || K <= 0) return CBL_ERR_BAD_ARG;
     if (!((C == 32 && G == 4) || (C == 64 && G == 8) || (C == 128 && G == 16) || (C == 256 && G == 32) || (C == 512 && G == 64))) return CBL_ERR_UNSUPPORTED;
-    return CBL_OK;
+    return width_ok ? CBL_OK : CBL_ERR_UNSUPPORTED;
 }
 inline int at_blocks(int n, int C)
 {
-    if (C > 64) return n < 1 ? 1 : (n > at_wide_blocks(C) ? at_wide_blocks(C) : n);                     // wide stages: one point per workgroup and trip
-    const int gpb = AT_BLOCK / C; const long long b = ((long long)n + gpb - 1) / gpb; return (int)(b < 1 ? 1 : (b > AT_MAX_BLOCKS ? AT_MAX_BLOCKS : b));
+    const int gpb = AT_BLOCK / C;                                     // wide stages: one point per workgroup and trip
+    const long long b = C > 64 ? n : ((long long)n + gpb - 1) / gpb;
+    return (int)(b < 1 ? 1 : (b > at_max_rows(C) ? at_max_rows(C) : b));
+}
+
+// the transposed table of idx (cbl_neighbor_transpose, n targets) that the gather-form backward entries take; `order` may be NULL
+struct AtTable { const int* order; const int* inv_start; const int* inv_src; };
+
+// Q1's sums = [grad_beta | grad_gamma | grad_Wa | grad_ba]: written to the four outputs and kept in `sums` for Q2 (BatchNorm's two means)
+void at_sum_q1(int C, int G, int nb, const float* partial, float* grad_bn_bias, float* grad_bn_weight, float* grad_Wa, float* grad_ba, float* sums, hipStream_t st)
+{
+    const int nv1 = 2 * C + G * C + G;
+    SumSegments s; s.dst[0] = grad_bn_bias; s.dst[1] = grad_bn_weight; s.dst[2] = grad_Wa; s.dst[3] = grad_ba;
+    s.begin[0] = 0; s.begin[1] = C; s.begin[2] = 2 * C; s.begin[3] = 2 * C + G * C; s.begin[4] = nv1;
+    hipLaunchKernelGGL(attn_sum_partials_kernel, dim3(cbl_div_up(nv1, 16)), dim3(256), 0, st, nv1, nb, partial, s, sums);
+}
+
+// partial rows [dW3C (C x 3, row-major like the weight) | db3C]: summed straight into the two outputs
+void at_sum_w3c(int C, int nb, const float* partial, float* grad_W3C, float* grad_b3C, hipStream_t st)
+{
+    const int nv2 = 4 * C;
+    SumSegments s; s.dst[0] = grad_W3C; s.dst[1] = grad_b3C; s.dst[2] = s.dst[3] = nullptr;
+    s.begin[0] = 0; s.begin[1] = 3 * C; s.begin[2] = s.begin[3] = s.begin[4] = nv2;
+    hipLaunchKernelGGL(attn_sum_partials_kernel, dim3(cbl_div_up(nv2, 16)), dim3(256), 0, st, nv2, nb, partial, s, (float*)nullptr);
+}
+
+// workgroups of the two gathers over the transposed table: the narrow kernels stride over (target, channel), the wide ones take a target per workgroup and trip
+inline int at_gather_blocks(int n, int C, int nb)
+{
+    return C > 64 ? nb : (int)cbl_round_up8((unsigned)cbl_grid_for((long long)n * C, AT_BLOCK, 8192));
 }
 
 }  // namespace
@@ -1023,16 +1053,28 @@ inline int at_blocks(int n, int C)
 CBL_EXPORT size_t cbl_attn_workspace_bytes(int C, int G)
 {
     const size_t per_block = (size_t)2 * C + (size_t)G * C + G;
-    return sizeof(float) * ((C > 64 ? at_wide_blocks(C) : AT_MAX_BLOCKS) * per_block + per_block) + 256;
+    return sizeof(float) * (at_max_rows(C) * per_block + per_block) + 256;
 }
 
-#define AT_DISPATCH(KERNEL, ...)                                                                                              \
+// one launch at the stage's width (`C`, on stream `st`): KERNEL_kernel<NARROW(C, G)> on AT_BLOCK threads for C = 32 / 64, KERNEL_wide_kernel<WIDE(C, G)> on C threads
+// above.  NARROW / WIDE name the kernel's template arguments: AT_C <C>, AT_CG <C, G>, AT_CG_NOSCATTER <C, G, SCATTER = false>
+#define AT_C(c, g) c
+#define AT_CG(c, g) c, g
+#define AT_CG_NOSCATTER(c, g) c, g, false
+#define AT_DISPATCH(KERNEL, NARROW, WIDE, grid, ...)                                                                            \
     do {                                                                                                                          \
-        if (C == 32)       hipLaunchKernelGGL((KERNEL##_kernel<32, 4>), dim3(nb), dim3(AT_BLOCK), 0, st, __VA_ARGS__);            \
-        else if (C == 64)  hipLaunchKernelGGL((KERNEL##_kernel<64, 8>), dim3(nb), dim3(AT_BLOCK), 0, st, __VA_ARGS__);            \
-        else if (C == 128) hipLaunchKernelGGL((KERNEL##_wide_kernel<128, 16>), dim3(nb), dim3(128), 0, st, __VA_ARGS__);          \
-        else if (C == 256) hipLaunchKernelGGL((KERNEL##_wide_kernel<256, 32>), dim3(nb), dim3(256), 0, st, __VA_ARGS__);          \
-        else               hipLaunchKernelGGL((KERNEL##_wide_kernel<512, 64>), dim3(nb), dim3(512), 0, st, __VA_ARGS__);          \
+        if (C == 32)       hipLaunchKernelGGL((KERNEL##_kernel<NARROW(32, 4)>), dim3(grid), dim3(AT_BLOCK), 0, st, __VA_ARGS__);  \
+        else if (C == 64)  hipLaunchKernelGGL((KERNEL##_kernel<NARROW(64, 8)>), dim3(grid), dim3(AT_BLOCK), 0, st, __VA_ARGS__);  \
+        else if (C == 128) hipLaunchKernelGGL((KERNEL##_wide_kernel<WIDE(128, 16)>), dim3(grid), dim3(128), 0, st, __VA_ARGS__);  \
+        else if (C == 256) hipLaunchKernelGGL((KERNEL##_wide_kernel<WIDE(256, 32)>), dim3(grid), dim3(256), 0, st, __VA_ARGS__);  \
+        else               hipLaunchKernelGGL((KERNEL##_wide_kernel<WIDE(512, 64)>), dim3(grid), dim3(512), 0, st, __VA_ARGS__);  \
+    } while (0)
+// a kernel that scatters into one of its outputs, with (`scatter`) or without that: the narrow kernels skip it for a NULL target, which the caller passes; the wide
+// ones have it compiled out (SCATTER = false)
+#define AT_DISPATCH_SCATTER(KERNEL, scatter, grid, ...)                                                                         \
+    do {                                                                                                                          \
+        if (scatter) AT_DISPATCH(KERNEL, AT_CG, AT_CG, grid, __VA_ARGS__);                                                        \
+        else         AT_DISPATCH(KERNEL, AT_CG, AT_CG_NOSCATTER, grid, __VA_ARGS__);                                              \
     } while (0)
 
 CBL_EXPORT int cbl_attn_w2_forward(int n, int K, int C, int G, const float* x_q, const float* x_k, const int* idx, const float* p1,
@@ -1050,11 +1092,7 @@ CBL_EXPORT int cbl_attn_w2_forward(int n, int K, int C, int G, const float* x_q,
     const int nb = at_blocks(n, C);
     float* partial = reinterpret_cast<float*>(workspace);
     if (training) {                                                   // eval mode: the caller put the running statistics into save_mean / save_invstd
-        if (C == 32)       hipLaunchKernelGGL(attn_w2_stats_kernel<32>, dim3(nb), dim3(AT_BLOCK), 0, st, n, K, x_q, x_k, idx, p1, W3C, b3C, partial);
-        else if (C == 64)  hipLaunchKernelGGL(attn_w2_stats_kernel<64>, dim3(nb), dim3(AT_BLOCK), 0, st, n, K, x_q, x_k, idx, p1, W3C, b3C, partial);
-        else if (C == 128) hipLaunchKernelGGL(attn_w2_stats_wide_kernel<128>, dim3(nb), dim3(128), 0, st, n, K, x_q, x_k, idx, p1, W3C, b3C, partial);
-        else if (C == 256) hipLaunchKernelGGL(attn_w2_stats_wide_kernel<256>, dim3(nb), dim3(256), 0, st, n, K, x_q, x_k, idx, p1, W3C, b3C, partial);
-        else               hipLaunchKernelGGL(attn_w2_stats_wide_kernel<512>, dim3(nb), dim3(512), 0, st, n, K, x_q, x_k, idx, p1, W3C, b3C, partial);
+        AT_DISPATCH(attn_w2_stats, AT_C, AT_C, nb, n, K, x_q, x_k, idx, p1, W3C, b3C, partial);
         hipLaunchKernelGGL(attn_bn_finalize_kernel, dim3(cbl_div_up(C, 16)), dim3(256), 0, st, (long long)n * K, C, nb, partial, eps, momentum,
                            running_mean, running_var, num_batches_tracked, save_mean, save_invstd);
     }
@@ -1065,39 +1103,7 @@ CBL_EXPORT int cbl_attn_w2_forward(int n, int K, int C, int G, const float* x_q,
         else         hipLaunchKernelGGL(attn_w2_forward_mfma_kernel<64>, dim3(g), dim3(AT_BLOCK), 0, st, n, K, x_q, x_k, idx, p1, W3C, b3C, save_mean, save_invstd, bn_weight, bn_bias, Wa, ba, w2);
         return cbl_status();
     }
-    AT_DISPATCH(attn_w2_forward, n, K, x_q, x_k, idx, p1, W3C, b3C, save_mean, save_invstd, bn_weight, bn_bias, Wa, ba, w2);
-    return cbl_status();
-}
-
-CBL_EXPORT int cbl_attn_w2_backward(int n, int K, int C, int G, const float* x_q, const float* x_k, const int* idx, const float* p1,
-                                    const float* W3C, const float* b3C, const float* bn_weight, const float* bn_bias,
-                                    const float* save_mean, const float* save_invstd, const float* Wa, const float* grad_w2,
-                                    float* grad_xq, float* grad_xk, float* grad_p1, float* grad_W3C, float* grad_b3C,
-                                    float* grad_bn_weight, float* grad_bn_bias, float* grad_Wa, float* grad_ba,
-                                    void* workspace, size_t workspace_bytes, void* stream)
-{
-    const int rc = at_check(n, K, C, G);
-    if (rc) return rc;
-    if (n == 0) return CBL_OK;
-    if (!x_q || !x_k || !idx || !p1 || !W3C || !b3C || !save_mean || !save_invstd || !Wa || !grad_w2 || !grad_xq || !grad_xk || !grad_p1 || !grad_W3C ||
-        !grad_b3C || !grad_bn_weight || !grad_bn_bias || !grad_Wa || !grad_ba || !workspace) return CBL_ERR_BAD_ARG;
-    if (workspace_bytes < cbl_attn_workspace_bytes(C, G)) return CBL_ERR_WORKSPACE;
-    hipStream_t st = cbl_stream(stream);
-    const int nb = at_blocks(n, C);
-    const int nv1 = 2 * C + G * C + G, nv2 = 4 * C;
-    float* partial = reinterpret_cast<float*>(workspace);
-    float* sums = partial + (size_t)(C > 64 ? at_wide_blocks(C) : AT_MAX_BLOCKS) * nv1;
-    AT_DISPATCH(attn_w2_bwd_reduce, n, K, x_q, x_k, idx, p1, W3C, b3C, save_mean, save_invstd, bn_weight, bn_bias, Wa, grad_w2, partial);
-    // Q1's sums = [grad_beta | grad_gamma | grad_Wa | grad_ba]: written to the four outputs and kept in `sums` for Q2 (BatchNorm's two means)
-    SumSegments s1; s1.dst[0] = grad_bn_bias; s1.dst[1] = grad_bn_weight; s1.dst[2] = grad_Wa; s1.dst[3] = grad_ba;
-    s1.begin[0] = 0; s1.begin[1] = C; s1.begin[2] = 2 * C; s1.begin[3] = 2 * C + G * C; s1.begin[4] = nv1;
-    hipLaunchKernelGGL(attn_sum_partials_kernel, dim3(cbl_div_up(nv1, 16)), dim3(256), 0, st, nv1, nb, partial, s1, sums);
-    AT_DISPATCH(attn_w2_bwd_apply, n, K, x_q, x_k, idx, p1, W3C, b3C, save_mean, save_invstd, bn_weight, bn_bias, Wa, grad_w2, sums,
-                grad_xq, grad_xk, grad_p1, partial);
-    // partial rows are [dW3C (C x 3, row-major like the weight) | db3C]: summed straight into the two outputs
-    SumSegments s2; s2.dst[0] = grad_W3C; s2.dst[1] = grad_b3C; s2.dst[2] = s2.dst[3] = nullptr;
-    s2.begin[0] = 0; s2.begin[1] = 3 * C; s2.begin[2] = s2.begin[3] = s2.begin[4] = nv2;
-    hipLaunchKernelGGL(attn_sum_partials_kernel, dim3(cbl_div_up(nv2, 16)), dim3(256), 0, st, nv2, nb, partial, s2, (float*)nullptr);
+    AT_DISPATCH(attn_w2_forward, AT_CG, AT_CG, nb, n, K, x_q, x_k, idx, p1, W3C, b3C, save_mean, save_invstd, bn_weight, bn_bias, Wa, ba, w2);
     return cbl_status();
 }
 
@@ -1110,7 +1116,7 @@ static int attn_agg_forward_impl(int n, int K, int C, int G, const float* x_v, c
     if (!x_v || !idx || !p1 || !W3C || !b3C || !a || !out) return CBL_ERR_BAD_ARG;
     hipStream_t st = cbl_stream(stream);
     const int nb = C > 64 ? (n < 1 ? 1 : (n > 2048 ? 2048 : n)) : (int)cbl_grid_for((long long)n * C, AT_BLOCK, 4096);   // no partial rows here: any grid
-    AT_DISPATCH(attn_agg_forward, n, K, x_v, idx, p1, W3C, b3C, a, a_out, out);
+    AT_DISPATCH(attn_agg_forward, AT_CG, AT_CG, nb, n, K, x_v, idx, p1, W3C, b3C, a, a_out, out);
     return cbl_status();
 }
 
@@ -1129,28 +1135,69 @@ CBL_EXPORT int cbl_attn_agg_softmax_forward(int n, int K, int C, int G, const fl
     return attn_agg_forward_impl(n, K, C, G, x_v, idx, p1, W3C, b3C, logits, a, out, stream);
 }
 
-static int attn_agg_backward_impl(int n, int K, int C, int G, const float* x_v, const int* idx, const float* p1, const float* W3C, const float* b3C,
-                                  const float* a, const float* grad_out, float* grad_xv, float* grad_p1, float* grad_W3C, float* grad_b3C, float* grad_a,
-                                  void* workspace, size_t workspace_bytes, int softmax, void* stream)
+// ---- the two backward passes, one host body each.  The exported entries below check the shape and the widths they take (at_check) and differ in `tr` only:
+// NULL = grad_xk / grad_xv scattered with float atomics into rows the caller has zeroed; a table = the scatter left out of the apply / aggregation kernel and one
+// gather launch over the table after it: grad_xk / grad_xv WRITTEN (no pre-zeroing), no atomics anywhere, deterministic.  Every other output is the same bits either way.
+static int attn_w2_backward_impl(int n, int K, int C, int G, const float* x_q, const float* x_k, const int* idx, const float* p1,
+                                 const float* W3C, const float* b3C, const float* bn_weight, const float* bn_bias,
+                                 const float* save_mean, const float* save_invstd, const float* Wa, const float* grad_w2, const AtTable* tr,
+                                 float* grad_xq, float* grad_xk, float* grad_p1, float* grad_W3C, float* grad_b3C,
+                                 float* grad_bn_weight, float* grad_bn_bias, float* grad_Wa, float* grad_ba,
+                                 void* workspace, size_t workspace_bytes, void* stream)
 {
-    const int rc = at_check(n, K, C, G);
-    if (rc) return rc;
     if (n == 0) return CBL_OK;
-    if (!x_v || !idx || !p1 || !W3C || !b3C || !a || !grad_out || !grad_xv || !grad_p1 || !grad_W3C || !grad_b3C || !grad_a || !workspace) return CBL_ERR_BAD_ARG;
+    if (!x_q || !x_k || !idx || !p1 || !W3C || !b3C || !save_mean || !save_invstd || !Wa || !grad_w2 || !grad_xq || !grad_xk || !grad_p1 || !grad_W3C ||
+        !grad_b3C || !grad_bn_weight || !grad_bn_bias || !grad_Wa || !grad_ba || !workspace || (tr && (!tr->inv_start || !tr->inv_src))) return CBL_ERR_BAD_ARG;
     if (workspace_bytes < cbl_attn_workspace_bytes(C, G)) return CBL_ERR_WORKSPACE;
     hipStream_t st = cbl_stream(stream);
     const int nb = at_blocks(n, C);
-    const int nv2 = 4 * C;
     float* partial = reinterpret_cast<float*>(workspace);
-    AT_DISPATCH(attn_agg_backward, n, K, x_v, idx, p1, W3C, b3C, a, grad_out, grad_xv, grad_p1, grad_a, partial, softmax);
-    SumSegments s2; s2.dst[0] = grad_W3C; s2.dst[1] = grad_b3C; s2.dst[2] = s2.dst[3] = nullptr;
-    s2.begin[0] = 0; s2.begin[1] = 3 * C; s2.begin[2] = s2.begin[3] = s2.begin[4] = nv2;
-    hipLaunchKernelGGL(attn_sum_partials_kernel, dim3(cbl_div_up(nv2, 16)), dim3(256), 0, st, nv2, nb, partial, s2, (float*)nullptr);
+    float* sums = partial + (size_t)at_max_rows(C) * (2 * C + G * C + G);
+    AT_DISPATCH(attn_w2_bwd_reduce, AT_CG, AT_CG, nb, n, K, x_q, x_k, idx, p1, W3C, b3C, save_mean, save_invstd, bn_weight, bn_bias, Wa, grad_w2, partial);
+    at_sum_q1(C, G, nb, partial, grad_bn_bias, grad_bn_weight, grad_Wa, grad_ba, sums, st);
+    AT_DISPATCH_SCATTER(attn_w2_bwd_apply, !tr, nb, n, K, x_q, x_k, idx, p1, W3C, b3C, save_mean, save_invstd, bn_weight, bn_bias, Wa, grad_w2, sums,
+                        grad_xq, tr ? (float*)nullptr : grad_xk, grad_p1, partial);
+    at_sum_w3c(C, nb, partial, grad_W3C, grad_b3C, st);
+    if (tr)
+        AT_DISPATCH(attn_w2_gxk_csr, AT_CG, AT_CG, at_gather_blocks(n, C, nb), n, K, cbl_fastdiv_make((unsigned)K), x_q, x_k, p1, W3C, b3C, save_mean, save_invstd,
+                    bn_weight, bn_bias, Wa, grad_w2, (const float*)sums, tr->order, tr->inv_start, tr->inv_src, grad_xk);
     return cbl_status();
 }
 
-// the same backward passes with the two scatters (grad_xk, grad_xv) as gathers over the transposed table of idx (C = 32 / 64; CBL_ERR_UNSUPPORTED
-// otherwise: the wide stages are small and keep their atomics): grad_xk / grad_xv are WRITTEN (no pre-zeroing), no atomics anywhere, deterministic
+static int attn_agg_backward_impl(int n, int K, int C, int G, const float* x_v, const int* idx, const float* p1, const float* W3C, const float* b3C,
+                                  const float* a, const float* grad_out, const AtTable* tr, float* grad_xv, float* grad_p1, float* grad_W3C, float* grad_b3C,
+                                  float* grad_a, void* workspace, size_t workspace_bytes, int softmax, void* stream)
+{
+    if (n == 0) return CBL_OK;
+    if (!x_v || !idx || !p1 || !W3C || !b3C || !a || !grad_out || !grad_xv || !grad_p1 || !grad_W3C || !grad_b3C || !grad_a || !workspace ||
+        (tr && (!tr->inv_start || !tr->inv_src))) return CBL_ERR_BAD_ARG;
+    if (workspace_bytes < cbl_attn_workspace_bytes(C, G)) return CBL_ERR_WORKSPACE;
+    hipStream_t st = cbl_stream(stream);
+    const int nb = at_blocks(n, C);
+    float* partial = reinterpret_cast<float*>(workspace);
+    AT_DISPATCH_SCATTER(attn_agg_backward, !tr, nb, n, K, x_v, idx, p1, W3C, b3C, a, grad_out, tr ? (float*)nullptr : grad_xv, grad_p1, grad_a, partial, softmax);
+    at_sum_w3c(C, nb, partial, grad_W3C, grad_b3C, st);
+    // (with softmax the kernel above has replaced grad_a by the gradient of the logits; the gather needs the softmax WEIGHTS `a`, which are its input)
+    if (tr)
+        AT_DISPATCH(attn_agg_gxv_csr, AT_CG, AT_CG, at_gather_blocks(n, C, nb), n, cbl_fastdiv_make((unsigned)K), a, grad_out, tr->order, tr->inv_start, tr->inv_src,
+                    grad_xv);
+    return cbl_status();
+}
+
+CBL_EXPORT int cbl_attn_w2_backward(int n, int K, int C, int G, const float* x_q, const float* x_k, const int* idx, const float* p1,
+                                    const float* W3C, const float* b3C, const float* bn_weight, const float* bn_bias,
+                                    const float* save_mean, const float* save_invstd, const float* Wa, const float* grad_w2,
+                                    float* grad_xq, float* grad_xk, float* grad_p1, float* grad_W3C, float* grad_b3C,
+                                    float* grad_bn_weight, float* grad_bn_bias, float* grad_Wa, float* grad_ba,
+                                    void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (const int rc = at_check(n, K, C, G)) return rc;
+    return attn_w2_backward_impl(n, K, C, G, x_q, x_k, idx, p1, W3C, b3C, bn_weight, bn_bias, save_mean, save_invstd, Wa, grad_w2, nullptr,
+                                 grad_xq, grad_xk, grad_p1, grad_W3C, grad_b3C, grad_bn_weight, grad_bn_bias, grad_Wa, grad_ba, workspace, workspace_bytes, stream);
+}
+
+// the gather form at C = 32 / 64 (CBL_ERR_UNSUPPORTED otherwise: the wide stages have entries of their own, cbl_attn_w2_backward_wide_csr /
+// cbl_attn_agg_backward_wide_csr, which the deterministic mode takes; outside it they keep their atomics)
 CBL_EXPORT int cbl_attn_w2_backward_csr(int n, int K, int C, int G, const float* x_q, const float* x_k, const int* idx, const float* p1,
                                         const float* W3C, const float* b3C, const float* bn_weight, const float* bn_bias,
                                         const float* save_mean, const float* save_invstd, const float* Wa, const float* grad_w2,
@@ -1159,81 +1206,13 @@ CBL_EXPORT int cbl_attn_w2_backward_csr(int n, int K, int C, int G, const float*
                                         float* grad_bn_weight, float* grad_bn_bias, float* grad_Wa, float* grad_ba,
                                         void* workspace, size_t workspace_bytes, void* stream)
 {
-    const int rc = at_check(n, K, C, G);
-    if (rc) return rc;
-    if (C > 64) return CBL_ERR_UNSUPPORTED;
-    if (n == 0) return CBL_OK;
-    if (!x_q || !x_k || !idx || !p1 || !W3C || !b3C || !save_mean || !save_invstd || !Wa || !grad_w2 || !grad_xq || !grad_xk || !grad_p1 || !grad_W3C ||
-        !grad_b3C || !grad_bn_weight || !grad_bn_bias || !grad_Wa || !grad_ba || !workspace || !inv_start || !inv_src) return CBL_ERR_BAD_ARG;
-    if (workspace_bytes < cbl_attn_workspace_bytes(C, G)) return CBL_ERR_WORKSPACE;
-    hipStream_t st = cbl_stream(stream);
-    const int nb = at_blocks(n, C);
-    const int nv1 = 2 * C + G * C + G, nv2 = 4 * C;
-    float* partial = reinterpret_cast<float*>(workspace);
-    float* sums = partial + (size_t)AT_MAX_BLOCKS * nv1;
-    AT_DISPATCH(attn_w2_bwd_reduce, n, K, x_q, x_k, idx, p1, W3C, b3C, save_mean, save_invstd, bn_weight, bn_bias, Wa, grad_w2, partial);
-    SumSegments s1; s1.dst[0] = grad_bn_bias; s1.dst[1] = grad_bn_weight; s1.dst[2] = grad_Wa; s1.dst[3] = grad_ba;
-    s1.begin[0] = 0; s1.begin[1] = C; s1.begin[2] = 2 * C; s1.begin[3] = 2 * C + G * C; s1.begin[4] = nv1;
-    hipLaunchKernelGGL(attn_sum_partials_kernel, dim3(cbl_div_up(nv1, 16)), dim3(256), 0, st, nv1, nb, partial, s1, sums);
-    AT_DISPATCH(attn_w2_bwd_apply, n, K, x_q, x_k, idx, p1, W3C, b3C, save_mean, save_invstd, bn_weight, bn_bias, Wa, grad_w2, sums,
-                grad_xq, (float*)nullptr, grad_p1, partial);
-    SumSegments s2; s2.dst[0] = grad_W3C; s2.dst[1] = grad_b3C; s2.dst[2] = s2.dst[3] = nullptr;
-    s2.begin[0] = 0; s2.begin[1] = 3 * C; s2.begin[2] = s2.begin[3] = s2.begin[4] = nv2;
-    hipLaunchKernelGGL(attn_sum_partials_kernel, dim3(cbl_div_up(nv2, 16)), dim3(256), 0, st, nv2, nb, partial, s2, (float*)nullptr);
-    const CblFastDiv dv = cbl_fastdiv_make((unsigned)K);
-    const unsigned g = cbl_round_up8((unsigned)cbl_grid_for((long long)n * C, AT_BLOCK, 8192));
-    if (C == 32) hipLaunchKernelGGL((attn_w2_gxk_csr_kernel<32, 4>), dim3(g), dim3(AT_BLOCK), 0, st, (unsigned)n, K, dv, x_q, x_k, p1, W3C, b3C, save_mean, save_invstd, bn_weight, bn_bias, Wa, grad_w2, sums, order, inv_start, inv_src, grad_xk);
-    else         hipLaunchKernelGGL((attn_w2_gxk_csr_kernel<64, 8>), dim3(g), dim3(AT_BLOCK), 0, st, (unsigned)n, K, dv, x_q, x_k, p1, W3C, b3C, save_mean, save_invstd, bn_weight, bn_bias, Wa, grad_w2, sums, order, inv_start, inv_src, grad_xk);
-    return cbl_status();
+    if (const int rc = at_check(n, K, C, G, C <= 64)) return rc;
+    const AtTable tr = {order, inv_start, inv_src};
+    return attn_w2_backward_impl(n, K, C, G, x_q, x_k, idx, p1, W3C, b3C, bn_weight, bn_bias, save_mean, save_invstd, Wa, grad_w2, &tr,
+                                 grad_xq, grad_xk, grad_p1, grad_W3C, grad_b3C, grad_bn_weight, grad_bn_bias, grad_Wa, grad_ba, workspace, workspace_bytes, stream);
 }
 
-CBL_EXPORT int cbl_attn_agg_backward_csr(int n, int K, int C, int G, const float* x_v, const int* idx, const float* p1, const float* W3C, const float* b3C,
-                                         const float* a, const float* grad_out, const int* order, const int* inv_start, const int* inv_src,
-                                         float* grad_xv, float* grad_p1, float* grad_W3C, float* grad_b3C, float* grad_a,
-                                         void* workspace, size_t workspace_bytes, int softmax, void* stream)
-{
-    const int rc = at_check(n, K, C, G);
-    if (rc) return rc;
-    if (C > 64) return CBL_ERR_UNSUPPORTED;
-    if (n == 0) return CBL_OK;
-    if (!x_v || !idx || !p1 || !W3C || !b3C || !a || !grad_out || !grad_xv || !grad_p1 || !grad_W3C || !grad_b3C || !grad_a || !workspace || !inv_start || !inv_src)
-        return CBL_ERR_BAD_ARG;
-    if (workspace_bytes < cbl_attn_workspace_bytes(C, G)) return CBL_ERR_WORKSPACE;
-    hipStream_t st = cbl_stream(stream);
-    const int nb = at_blocks(n, C);
-    const int nv2 = 4 * C;
-    float* partial = reinterpret_cast<float*>(workspace);
-    AT_DISPATCH(attn_agg_backward, n, K, x_v, idx, p1, W3C, b3C, a, grad_out, (float*)nullptr, grad_p1, grad_a, partial, softmax);
-    SumSegments s2; s2.dst[0] = grad_W3C; s2.dst[1] = grad_b3C; s2.dst[2] = s2.dst[3] = nullptr;
-    s2.begin[0] = 0; s2.begin[1] = 3 * C; s2.begin[2] = s2.begin[3] = s2.begin[4] = nv2;
-    hipLaunchKernelGGL(attn_sum_partials_kernel, dim3(cbl_div_up(nv2, 16)), dim3(256), 0, st, nv2, nb, partial, s2, (float*)nullptr);
-    // (with softmax the kernel above has replaced grad_a by the gradient of the logits; the gather needs the softmax WEIGHTS `a`, which are its input)
-    const CblFastDiv dv = cbl_fastdiv_make((unsigned)K);
-    const unsigned g = cbl_round_up8((unsigned)cbl_grid_for((long long)n * C, AT_BLOCK, 8192));
-    if (C == 32) hipLaunchKernelGGL((attn_agg_gxv_csr_kernel<32, 4>), dim3(g), dim3(AT_BLOCK), 0, st, (unsigned)n, dv, a, grad_out, order, inv_start, inv_src, grad_xv);
-    else         hipLaunchKernelGGL((attn_agg_gxv_csr_kernel<64, 8>), dim3(g), dim3(AT_BLOCK), 0, st, (unsigned)n, dv, a, grad_out, order, inv_start, inv_src, grad_xv);
-    return cbl_status();
-}
-
-// wide kernels only (C = 128 / 256 / 512, checked by the caller); KERNEL with its template arguments' tail, e.g. AT_DISPATCH_WIDE(attn_w2_bwd_apply_wide_kernel, (, false), ...)
-#define AT_UNPAREN(...) __VA_ARGS__
-#define AT_DISPATCH_WIDE(KERNEL, TAIL, ...)                                                                                    \
-    do {                                                                                                                          \
-        if (C == 128)      hipLaunchKernelGGL((KERNEL<128, 16 AT_UNPAREN TAIL>), dim3(nb), dim3(128), 0, st, __VA_ARGS__);         \
-        else if (C == 256) hipLaunchKernelGGL((KERNEL<256, 32 AT_UNPAREN TAIL>), dim3(nb), dim3(256), 0, st, __VA_ARGS__);         \
-        else               hipLaunchKernelGGL((KERNEL<512, 64 AT_UNPAREN TAIL>), dim3(nb), dim3(512), 0, st, __VA_ARGS__);         \
-    } while (0)
-
-static inline int at_check_wide(int n, int K, int C, int G)
-{
-    const int rc = at_check(n, K, C, G);
-    if (rc) return rc;
-    return C > 64 ? CBL_OK : CBL_ERR_UNSUPPORTED;
-}
-
-// cbl_attn_w2_backward_csr / cbl_attn_agg_backward_csr for the WIDE stages (C = 128 / 256 / 512, G = C / 8; CBL_ERR_UNSUPPORTED otherwise): the passes of
-// cbl_attn_w2_backward / cbl_attn_agg_backward with the scatter compiled out of the apply / aggregation kernel, then one gather launch over the transposed
-// table — grad_xk / grad_xv WRITTEN (no pre-zeroing), no atomics anywhere, deterministic.  The caller owns every buffer; same workspace as the scatter entries.
+// the gather form for the WIDE stages (C = 128 / 256 / 512, G = C / 8; CBL_ERR_UNSUPPORTED otherwise).  The caller owns every buffer; same workspace as the scatter entries.
 CBL_EXPORT int cbl_attn_w2_backward_wide_csr(int n, int K, int C, int G, const float* x_q, const float* x_k, const int* idx, const float* p1,
                                              const float* W3C, const float* b3C, const float* bn_weight, const float* bn_bias,
                                              const float* save_mean, const float* save_invstd, const float* Wa, const float* grad_w2,
@@ -1242,62 +1221,19 @@ CBL_EXPORT int cbl_attn_w2_backward_wide_csr(int n, int K, int C, int G, const f
                                              float* grad_bn_weight, float* grad_bn_bias, float* grad_Wa, float* grad_ba,
                                              void* workspace, size_t workspace_bytes, void* stream)
 {
-    const int rc = at_check_wide(n, K, C, G);
-    if (rc) return rc;
-    if (n == 0) return CBL_OK;
-    if (!x_q || !x_k || !idx || !p1 || !W3C || !b3C || !save_mean || !save_invstd || !Wa || !grad_w2 || !grad_xq || !grad_xk || !grad_p1 || !grad_W3C ||
-        !grad_b3C || !grad_bn_weight || !grad_bn_bias || !grad_Wa || !grad_ba || !workspace || !inv_start || !inv_src) return CBL_ERR_BAD_ARG;
-    if (workspace_bytes < cbl_attn_workspace_bytes(C, G)) return CBL_ERR_WORKSPACE;
-    hipStream_t st = cbl_stream(stream);
-    const int nb = at_blocks(n, C);
-    const int nv1 = 2 * C + G * C + G, nv2 = 4 * C;
-    float* partial = reinterpret_cast<float*>(workspace);
-    float* sums = partial + (size_t)at_wide_blocks(C) * nv1;
-    AT_DISPATCH(attn_w2_bwd_reduce, n, K, x_q, x_k, idx, p1, W3C, b3C, save_mean, save_invstd, bn_weight, bn_bias, Wa, grad_w2, partial);
-    SumSegments s1; s1.dst[0] = grad_bn_bias; s1.dst[1] = grad_bn_weight; s1.dst[2] = grad_Wa; s1.dst[3] = grad_ba;
-    s1.begin[0] = 0; s1.begin[1] = C; s1.begin[2] = 2 * C; s1.begin[3] = 2 * C + G * C; s1.begin[4] = nv1;
-    hipLaunchKernelGGL(attn_sum_partials_kernel, dim3(cbl_div_up(nv1, 16)), dim3(256), 0, st, nv1, nb, partial, s1, sums);
-    AT_DISPATCH_WIDE(attn_w2_bwd_apply_wide_kernel, (, false), n, K, x_q, x_k, idx, p1, W3C, b3C, save_mean, save_invstd, bn_weight, bn_bias, Wa, grad_w2, sums,
-                     grad_xq, (float*)nullptr, grad_p1, partial);
-    SumSegments s2; s2.dst[0] = grad_W3C; s2.dst[1] = grad_b3C; s2.dst[2] = s2.dst[3] = nullptr;
-    s2.begin[0] = 0; s2.begin[1] = 3 * C; s2.begin[2] = s2.begin[3] = s2.begin[4] = nv2;
-    hipLaunchKernelGGL(attn_sum_partials_kernel, dim3(cbl_div_up(nv2, 16)), dim3(256), 0, st, nv2, nb, partial, s2, (float*)nullptr);
-    const CblFastDiv dv = cbl_fastdiv_make((unsigned)K);
-    AT_DISPATCH_WIDE(attn_w2_gxk_csr_wide_kernel, (), n, K, dv, x_q, x_k, p1, W3C, b3C, save_mean, save_invstd, bn_weight, bn_bias, Wa, grad_w2, (const float*)sums,
-                     order, inv_start, inv_src, grad_xk);
-    return cbl_status();
-}
-
-CBL_EXPORT int cbl_attn_agg_backward_wide_csr(int n, int K, int C, int G, const float* x_v, const int* idx, const float* p1, const float* W3C, const float* b3C,
-                                              const float* a, const float* grad_out, const int* order, const int* inv_start, const int* inv_src,
-                                              float* grad_xv, float* grad_p1, float* grad_W3C, float* grad_b3C, float* grad_a,
-                                              void* workspace, size_t workspace_bytes, int softmax, void* stream)
-{
-    const int rc = at_check_wide(n, K, C, G);
-    if (rc) return rc;
-    if (n == 0) return CBL_OK;
-    if (!x_v || !idx || !p1 || !W3C || !b3C || !a || !grad_out || !grad_xv || !grad_p1 || !grad_W3C || !grad_b3C || !grad_a || !workspace || !inv_start || !inv_src)
-        return CBL_ERR_BAD_ARG;
-    if (workspace_bytes < cbl_attn_workspace_bytes(C, G)) return CBL_ERR_WORKSPACE;
-    hipStream_t st = cbl_stream(stream);
-    const int nb = at_blocks(n, C);
-    const int nv2 = 4 * C;
-    float* partial = reinterpret_cast<float*>(workspace);
-    AT_DISPATCH_WIDE(attn_agg_backward_wide_kernel, (, false), n, K, x_v, idx, p1, W3C, b3C, a, grad_out, (float*)nullptr, grad_p1, grad_a, partial, softmax);
-    SumSegments s2; s2.dst[0] = grad_W3C; s2.dst[1] = grad_b3C; s2.dst[2] = s2.dst[3] = nullptr;
-    s2.begin[0] = 0; s2.begin[1] = 3 * C; s2.begin[2] = s2.begin[3] = s2.begin[4] = nv2;
-    hipLaunchKernelGGL(attn_sum_partials_kernel, dim3(cbl_div_up(nv2, 16)), dim3(256), 0, st, nv2, nb, partial, s2, (float*)nullptr);
-    // (with softmax the kernel above has replaced grad_a by the gradient of the logits; the gather needs the softmax WEIGHTS `a`, which are its input)
-    const CblFastDiv dv = cbl_fastdiv_make((unsigned)K);
-    AT_DISPATCH_WIDE(attn_agg_gxv_csr_wide_kernel, (), n, dv, a, grad_out, order, inv_start, inv_src, grad_xv);
-    return cbl_status();
+    if (const int rc = at_check(n, K, C, G, C > 64)) return rc;
+    const AtTable tr = {order, inv_start, inv_src};
+    return attn_w2_backward_impl(n, K, C, G, x_q, x_k, idx, p1, W3C, b3C, bn_weight, bn_bias, save_mean, save_invstd, Wa, grad_w2, &tr,
+                                 grad_xq, grad_xk, grad_p1, grad_W3C, grad_b3C, grad_bn_weight, grad_bn_bias, grad_Wa, grad_ba, workspace, workspace_bytes, stream);
 }
 
 CBL_EXPORT int cbl_attn_agg_backward(int n, int K, int C, int G, const float* x_v, const int* idx, const float* p1, const float* W3C, const float* b3C,
                                      const float* a, const float* grad_out, float* grad_xv, float* grad_p1, float* grad_W3C, float* grad_b3C, float* grad_a,
                                      void* workspace, size_t workspace_bytes, void* stream)
 {
-    return attn_agg_backward_impl(n, K, C, G, x_v, idx, p1, W3C, b3C, a, grad_out, grad_xv, grad_p1, grad_W3C, grad_b3C, grad_a, workspace, workspace_bytes, 0, stream);
+    if (const int rc = at_check(n, K, C, G)) return rc;
+    return attn_agg_backward_impl(n, K, C, G, x_v, idx, p1, W3C, b3C, a, grad_out, nullptr, grad_xv, grad_p1, grad_W3C, grad_b3C, grad_a, workspace, workspace_bytes, 0,
+                                  stream);
 }
 
 // backward of cbl_attn_agg_softmax_forward: `a` = the softmax weights it wrote, grad_logits (n, K, G) = a (da - sum over K of a da)
@@ -1305,6 +1241,29 @@ CBL_EXPORT int cbl_attn_agg_softmax_backward(int n, int K, int C, int G, const f
                                              const float* a, const float* grad_out, float* grad_xv, float* grad_p1, float* grad_W3C, float* grad_b3C,
                                              float* grad_logits, void* workspace, size_t workspace_bytes, void* stream)
 {
-    return attn_agg_backward_impl(n, K, C, G, x_v, idx, p1, W3C, b3C, a, grad_out, grad_xv, grad_p1, grad_W3C, grad_b3C, grad_logits, workspace, workspace_bytes, 1,
-                                  stream);
+    if (const int rc = at_check(n, K, C, G)) return rc;
+    return attn_agg_backward_impl(n, K, C, G, x_v, idx, p1, W3C, b3C, a, grad_out, nullptr, grad_xv, grad_p1, grad_W3C, grad_b3C, grad_logits, workspace,
+                                  workspace_bytes, 1, stream);
+}
+
+CBL_EXPORT int cbl_attn_agg_backward_csr(int n, int K, int C, int G, const float* x_v, const int* idx, const float* p1, const float* W3C, const float* b3C,
+                                         const float* a, const float* grad_out, const int* order, const int* inv_start, const int* inv_src,
+                                         float* grad_xv, float* grad_p1, float* grad_W3C, float* grad_b3C, float* grad_a,
+                                         void* workspace, size_t workspace_bytes, int softmax, void* stream)
+{
+    if (const int rc = at_check(n, K, C, G, C <= 64)) return rc;
+    const AtTable tr = {order, inv_start, inv_src};
+    return attn_agg_backward_impl(n, K, C, G, x_v, idx, p1, W3C, b3C, a, grad_out, &tr, grad_xv, grad_p1, grad_W3C, grad_b3C, grad_a, workspace, workspace_bytes,
+                                  softmax, stream);
+}
+
+CBL_EXPORT int cbl_attn_agg_backward_wide_csr(int n, int K, int C, int G, const float* x_v, const int* idx, const float* p1, const float* W3C, const float* b3C,
+                                              const float* a, const float* grad_out, const int* order, const int* inv_start, const int* inv_src,
+                                              float* grad_xv, float* grad_p1, float* grad_W3C, float* grad_b3C, float* grad_a,
+                                              void* workspace, size_t workspace_bytes, int softmax, void* stream)
+{
+    if (const int rc = at_check(n, K, C, G, C > 64)) return rc;
+    const AtTable tr = {order, inv_start, inv_src};
+    return attn_agg_backward_impl(n, K, C, G, x_v, idx, p1, W3C, b3C, a, grad_out, &tr, grad_xv, grad_p1, grad_W3C, grad_b3C, grad_a, workspace, workspace_bytes,
+                                  softmax, stream);
 }

@@ -161,21 +161,17 @@ def _wide_backward(x_q, x_k, x_v, idx, kept, params, g_out, g_qkv):
     L = _lib.lib()
     g_params = [torch.empty_like(t) for t in params]
     ws = _workspace(L.cbl_pt_layer_wide_workspace_bytes(_i(n), _i(K), _i(C)), x_q.device)
+    what, table = "cbl_pt_layer_wide_backward", []
     if neighbor_state.is_deterministic():
         from . import pointops
         tr = pointops.neighbor_transpose(idx, n, build=True)
         if tr is None:
             raise _lib.CblError("deterministic pt_layer wide backward needs the transposed neighbour table (n <= %d)" % MAX_POINTS)
-        order, inv_start, inv_src = tr
-        _lib.check(L.cbl_pt_layer_wide_backward_csr(_i(n), _i(K), _i(C), _P(x_q), _P(x_k), _P(x_v), _P(idx), _P(order), _P(inv_start), _P(inv_src), _P(gamma_p),
-                                                    _P(W3C), _P(b3C), _P(gamma_c), _P(beta_c), _P(Wa), _P(gamma_g), _P(Wb), _P(p_r), _P(p0), _P(p1), _P(w2), _P(a),
-                                                    _P(consts), _P(bnc), _P(g_out.contiguous()), _P(g_qkv[0]), _P(g_qkv[1]), _P(g_qkv[2]), *[_P(t) for t in g_params],
-                                                    _P(ws), ctypes.c_size_t(ws.numel()), _lib.stream_of(x_q)), "cbl_pt_layer_wide_backward_csr")
-        return g_params
-    _lib.check(L.cbl_pt_layer_wide_backward(_i(n), _i(K), _i(C), _P(x_q), _P(x_k), _P(x_v), _P(idx), _P(gamma_p), _P(W3C), _P(b3C), _P(gamma_c), _P(beta_c),
-                                            _P(Wa), _P(gamma_g), _P(Wb), _P(p_r), _P(p0), _P(p1), _P(w2), _P(a), _P(consts), _P(bnc), _P(g_out.contiguous()),
-                                            _P(g_qkv[0]), _P(g_qkv[1]), _P(g_qkv[2]), *[_P(t) for t in g_params], _P(ws), ctypes.c_size_t(ws.numel()),
-                                            _lib.stream_of(x_q)), "cbl_pt_layer_wide_backward")
+        what, table = "cbl_pt_layer_wide_backward_csr", [_P(t) for t in tr]    # order, inv_start, inv_src
+    _lib.check(getattr(L, what)(_i(n), _i(K), _i(C), _P(x_q), _P(x_k), _P(x_v), _P(idx), *table, _P(gamma_p), _P(W3C), _P(b3C), _P(gamma_c), _P(beta_c),
+                                _P(Wa), _P(gamma_g), _P(Wb), _P(p_r), _P(p0), _P(p1), _P(w2), _P(a), _P(consts), _P(bnc), _P(g_out.contiguous()),
+                                _P(g_qkv[0]), _P(g_qkv[1]), _P(g_qkv[2]), *[_P(t) for t in g_params], _P(ws), ctypes.c_size_t(ws.numel()),
+                                _lib.stream_of(x_q)), what)
     return g_params
 
 

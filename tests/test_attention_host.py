@@ -188,3 +188,73 @@ def test_three_projections_in_one_launch(host, rows, C):
     for p in range(3):
         close(gW[p], gy[p].astype(np.float64).T @ x64, 1e-5)
         close(gb[p], gy[p].astype(np.float64).sum(0), 1e-5)
+
+
+# ---- the return-code contract of the seven backward entries: shape, then the width the entry refuses, then n == 0, then NULL pointers, then the workspace
+_TABLE = ("order", "inv_start", "inv_src")
+_W2 = (("x_q", "x_k", "idx", "p1", "W3C", "b3C", "gamma", "beta", "mean", "invstd", "Wa", "g_w2"),
+       ("g_xq", "g_xk", "g_p1", "g_W3C", "g_b3C", "g_gamma", "g_beta", "g_Wa", "g_ba"))
+_AGG = (("x_v", "idx", "p1", "W3C", "b3C", "logits", "g_out"), ("g_xv", "g_p1", "g_W3C", "g_b3C", "g_a"))
+# entry -> ((inputs, outputs), takes the transposed table, takes the softmax flag, the widths it accepts)
+BACKWARD_ENTRIES = {
+    "cbl_attn_w2_backward": (_W2, False, False, (32, 128)),
+    "cbl_attn_w2_backward_csr": (_W2, True, False, (32,)),
+    "cbl_attn_w2_backward_wide_csr": (_W2, True, False, (128,)),
+    "cbl_attn_agg_backward": (_AGG, False, False, (32, 128)),
+    "cbl_attn_agg_softmax_backward": (_AGG, False, False, (32, 128)),
+    "cbl_attn_agg_backward_csr": (_AGG, True, True, (32,)),
+    "cbl_attn_agg_backward_wide_csr": (_AGG, True, True, (128,)),
+}
+OK, BAD_ARG, WORKSPACE, UNSUPPORTED = 0, -1, -2, -3
+
+
+def backward_buffers(host, n, K, C, G):
+    """every argument of the backward entries at this shape: inputs random, a valid transposed table, outputs filled with NaN"""
+    rng = np.random.default_rng(C + G)
+    f = lambda *s: np.ascontiguousarray(rng.normal(size=s), np.float32)
+    idx = rng.integers(0, n, (n, K)).astype(np.int32)
+    b = dict(x_q=f(n, C), x_k=f(n, C), x_v=f(n, C), idx=idx, p1=np.abs(f(n, K, 3)), W3C=f(C, 3), b3C=f(C), gamma=f(C), beta=f(C), mean=f(C),
+             invstd=np.abs(f(C)) + 0.5, Wa=f(G, C), g_w2=f(n, K, G), logits=f(n, K, G), g_out=f(n, C), order=np.arange(n, dtype=np.int32))
+    b["inv_start"], b["inv_src"] = transposed(host, idx)
+    shapes = dict(g_xq=(n, C), g_xk=(n, C), g_xv=(n, C), g_p1=(n, K, 3), g_W3C=(C, 3), g_b3C=(C,), g_gamma=(C,), g_beta=(C,), g_Wa=(G, C), g_ba=(G,), g_a=(n, K, G))
+    b.update({k: np.full(s, np.nan, np.float32) for k, s in shapes.items()})
+    nbytes = host.cbl_attn_workspace_bytes(C, G)
+    b["ws"] = np.zeros(nbytes + 64, np.uint8)
+    return b, nbytes
+
+
+def call_backward(host, name, n, K, C, G, b, nbytes):
+    (ins, outs), table, softmax, _ = BACKWARD_ENTRIES[name]
+    args = [n, K, C, G] + [P(b.get(k)) for k in ins] + ([P(b.get(k)) for k in _TABLE] if table else []) + [P(b.get(k)) for k in outs]
+    args += [P(b.get("ws")), ctypes.c_size_t(nbytes)] + ([1] if softmax else []) + [None]
+    return getattr(host, name)(*args)
+
+
+@pytest.mark.parametrize("C", [32, 128])
+@pytest.mark.parametrize("name", sorted(BACKWARD_ENTRIES))
+def test_backward_entries_return_codes(host, name, C):
+    n, K, G = 5, 4, C // 8
+    (ins, outs), table, softmax, accepted = BACKWARD_ENTRIES[name]
+    b, nbytes = backward_buffers(host, n, K, C, G)
+
+    def refused(rc, want, bufs=b):
+        assert rc == want, (rc, want)
+        assert all(np.isnan(bufs[k]).all() for k in outs)              # nothing was launched
+
+    refused(call_backward(host, name, n, 0, C, G, b, nbytes), BAD_ARG)                      # the shape comes first, at any width
+    refused(call_backward(host, name, -1, K, C, G, b, nbytes), BAD_ARG)
+    b48, nbytes48 = backward_buffers(host, n, K, 48, 6)
+    refused(call_backward(host, name, n, K, 48, 6, b48, nbytes48), UNSUPPORTED, b48)
+    refused(call_backward(host, name, n, K, C, G + 1, b, nbytes), UNSUPPORTED)
+    if C not in accepted:                                              # the width this entry leaves to its twin: refused before n == 0 is looked at
+        refused(call_backward(host, name, n, K, C, G, b, nbytes), UNSUPPORTED)
+        assert call_backward(host, name, 0, K, C, G, {}, 0) == UNSUPPORTED
+        return
+    assert call_backward(host, name, 0, K, C, G, {}, 0) == OK         # n == 0 with every pointer NULL: before the pointer and workspace checks
+    for k in outs + ("ws",) + (("inv_start", "inv_src") if table else ()):
+        refused(call_backward(host, name, n, K, C, G, dict(b, **{k: None}), nbytes), BAD_ARG)
+    refused(call_backward(host, name, n, K, C, G, dict(b, ws=None), nbytes - 1), BAD_ARG)   # NULL pointers before the workspace size
+    refused(call_backward(host, name, n, K, C, G, b, nbytes - 1), WORKSPACE)
+    if table:                                                          # `order` may be NULL (targets in index order): the pass runs
+        assert call_backward(host, name, n, K, C, G, dict(b, order=None), nbytes) == OK
+        assert not any(np.isnan(b[k]).any() for k in outs)
