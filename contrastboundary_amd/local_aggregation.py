@@ -1,6 +1,8 @@
 """Host mirror of the TF-side local aggregation operators (value semantics of the TF1 graph code):
     kpconv (PseudoGrid)   /root/reference/tensorflow/models/local_aggregation_operators.py:620-746
     adaptive_weight       ...:316-500 (shipped options, config/s3dis/adapt.yaml:19-26)
+    pospool               ...:15-250
+    pointwise_mlp         ...:503-617 (fc_num 1; its batch norm and activation sit INSIDE the per-pair MLP, before the reduction: part of the kernels)
     ind_max_pool / ind_closest_pool   /root/reference/tensorflow/models/basic_operators.py:155-192
 Arguments keep the reference's names and order (query_points, support_points, neighbors_indices, features, ...); the
 trainable variables the TF code creates inside its variable scope (kernel weights, FC weight/bias) are explicit tensors.
@@ -215,6 +217,160 @@ def pospool(query_points, support_points, neighbors_indices, features, radius, p
         raise NotImplementedError("Reduction {} not supported in PosPool".format(reduction))
     return _PosPool.apply(query_points, support_points, neighbors_indices, features, float(radius), POSPOOL_EMBEDDINGS[position_embedding],
                           _POSPOOL_REDUCTIONS[reduction])
+
+
+POINTWISE_MLP_INPUTS = ("dp_fj", "fi_df", "dp_fi_df", "dp_fi_df_fj")
+_PW_REDUCTIONS = {"sum": 0, "mean": 1, "max": 2}
+_PW_ACTIVATIONS = {"relu": 1, "leaky_relu": 2}          # any other string is the identity (basic_operators.py:285-289)
+
+
+class _PointWiseMLP(Function):
+    """the two entries of csrc/pointwise_mlp.hip around the folded per-point terms (cbl_amd.h, a14 PointWiseMLP)"""
+
+    @staticmethod
+    def forward(ctx, query_points, support_points, neighbors_indices, center_term, neighbor_term, w_pos, gamma, beta, moving_mean, moving_variance,
+                radius, bn_mode, act, red, momentum, eps):
+        n, K = neighbors_indices.shape
+        n0, C = neighbor_term.shape
+        L = _lib.lib()
+        dev = neighbor_term.device
+        st = _lib.stream_of(neighbor_term)
+        pad = torch.empty(1, dtype=torch.int32, device=dev)
+        if red == 1:
+            _lib.check(L.cbl_index_max(ctypes.c_longlong(n * K), _lib.ptr(neighbors_indices), _lib.ptr(pad), st), "cbl_index_max")
+        out = torch.empty((n, C), dtype=torch.float32, device=dev)
+        save_mean = torch.empty(C, dtype=torch.float32, device=dev) if bn_mode else None
+        save_invstd = torch.empty(C, dtype=torch.float32, device=dev) if bn_mode else None
+        ws = torch.empty(max(L.cbl_pointwise_mlp_workspace_bytes(_i(n), _i(n0), _i(K), _i(C)), 1), dtype=torch.uint8, device=dev)
+        _lib.check(L.cbl_pointwise_mlp_forward(_i(n), _i(n0), _i(K), _i(C), _lib.ptr(query_points), _lib.ptr(support_points), _lib.ptr(neighbors_indices),
+                                               _lib.ptr(center_term), _lib.ptr(neighbor_term), _lib.ptr(w_pos), _f(radius), _i(bn_mode), _lib.ptr(gamma),
+                                               _lib.ptr(beta), _f(eps), _f(momentum), _lib.ptr(moving_mean), _lib.ptr(moving_variance), _i(act), _i(red),
+                                               _lib.ptr(pad), _lib.ptr(save_mean), _lib.ptr(save_invstd), _lib.ptr(out), _lib.ptr(ws),
+                                               ctypes.c_size_t(ws.numel()), st), "cbl_pointwise_mlp_forward")
+        ctx.save_for_backward(query_points, support_points, neighbors_indices, center_term, neighbor_term, w_pos, gamma, beta, save_mean, save_invstd, pad, out)
+        ctx.cfg = (radius, bn_mode, act, red)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        q, s, idx, cen, nbr, wp, gamma, beta, save_mean, save_invstd, pad, out = ctx.saved_tensors
+        radius, bn_mode, act, red = ctx.cfg
+        n, K = idx.shape
+        n0, C = nbr.shape
+        grad_out = grad_out.contiguous()
+        L = _lib.lib()
+        dev = nbr.device
+        st = _lib.stream_of(nbr)
+        from . import pointops
+        need = ctx.needs_input_grad
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        gc = new(n, C) if cen is not None and need[3] else None
+        gn = new(n0, C) if need[4] else None
+        gwp = new(3, C) if wp is not None and need[5] else None
+        gg = new(C) if gamma is not None and need[6] else None
+        gb = new(C) if beta is not None and need[7] else None
+        order = inv_start = inv_src = None
+        if gn is not None:
+            tr = pointops.neighbor_transpose(idx, n0, build=True)
+            if tr is None:
+                raise NotImplementedError("pointwise_mlp: no transposed neighbour table for more than 2^20 support points, and there is no scatter form")
+            order, inv_start, inv_src = tr
+        ws = torch.empty(max(L.cbl_pointwise_mlp_workspace_bytes(_i(n), _i(n0), _i(K), _i(C)), 1), dtype=torch.uint8, device=dev)
+        _lib.check(L.cbl_pointwise_mlp_backward_csr(_i(n), _i(n0), _i(K), _i(C), _lib.ptr(q), _lib.ptr(s), _lib.ptr(idx), _lib.ptr(cen), _lib.ptr(nbr),
+                                                    _lib.ptr(wp), _f(radius), _i(bn_mode), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(save_mean),
+                                                    _lib.ptr(save_invstd), _i(act), _i(red), _lib.ptr(pad), _lib.ptr(out), _lib.ptr(grad_out),
+                                                    _lib.ptr(order), _lib.ptr(inv_start), _lib.ptr(inv_src), _lib.ptr(gc), _lib.ptr(gn), _lib.ptr(gwp),
+                                                    _lib.ptr(gg), _lib.ptr(gb), _lib.ptr(ws), ctypes.c_size_t(ws.numel()), st), "cbl_pointwise_mlp_backward_csr")
+        gcen = None
+        if gc is not None:
+            # per-query rows onto the centre rows they came from (shadow_features[idx[:, 0]]): the row scatter as a gather over the table of that one column
+            idx0 = idx[:, :1].contiguous()
+            tr0 = pointops.neighbor_transpose(idx0, n0, build=True)
+            if tr0 is None:
+                raise NotImplementedError("pointwise_mlp: no transposed neighbour table for more than 2^20 support points, and there is no scatter form")
+            gcen = new(n0, C)
+            _lib.check(L.cbl_grouping_backward_csr_rows(_i(n0), _i(C), _i(C), _i(0), _lib.ptr(gc), _lib.ptr(tr0[0]), _lib.ptr(tr0[1]), _lib.ptr(tr0[2]),
+                                                        _lib.ptr(gcen), st), "cbl_grouping_backward_csr_rows")
+        return (None, None, None, gcen, gn, gwp, gg, gb) + (None,) * 8
+
+
+def pointwise_mlp(query_points, support_points, neighbors_indices, features, radius, weights, gamma=None, beta=None, moving_mean=None,
+                  moving_variance=None, *, local_input_feature="dp_fj", reduction="max", activation_fn="relu", is_training=True, bn_momentum=0.98,
+                  bn_eps=1e-3, fc_num=1):
+    """PointWiseMLP (n, out_fdim)  (tensorflow/models/local_aggregation_operators.py:503-617; options as config.pointwisemlp.*) with fc_num 1.
+    weights: the TF variable fc_1/weights (D_in, C_out), rows in the concatenation order of :573-584; gamma / beta: its batch norm (gamma None: bn=False);
+    moving_mean / moving_variance: updated in place when training (TF convention), used when not.
+    One FC layer is linear in the concatenated blocks: y = dp @ W_p + (f @ (W_fi - W_df))[idx[:, 0]] + (f @ (W_df + W_fj))[idx] — the two per-point products
+    are dense layers here (autograd carries the fold and the weight gradient), the per-pair part is csrc/pointwise_mlp.hip."""
+    if fc_num != 1:
+        raise NotImplementedError("pointwisemlp.fc_num {}: only fc_num 1 is implemented (the fold of the FC layer holds for one layer)".format(fc_num))
+    _chk(query_points, torch.float32, "query_points"); _chk(support_points, torch.float32, "support_points")
+    _chk(neighbors_indices, torch.int32, "neighbors_indices"); _chk(features, torch.float32, "features")
+    _chk(weights, torch.float32, "weights")
+    for t, name in ((gamma, "gamma"), (beta, "beta"), (moving_mean, "moving_mean"), (moving_variance, "moving_variance")):
+        if t is not None:
+            _chk(t, torch.float32, name)
+    if local_input_feature not in POINTWISE_MLP_INPUTS:
+        raise NotImplementedError("local_input_feature {} not supported in Point-wise MLP".format(local_input_feature))
+    if reduction not in _PW_REDUCTIONS:
+        raise NotImplementedError("Reduction {} not supported in Point-wise MLP.".format(reduction))
+    C, C_out, K = features.shape[1], weights.shape[1], neighbors_indices.shape[1]
+    has_dp, has_fi, has_fj = local_input_feature.startswith("dp"), "fi_df" in local_input_feature, local_input_feature.endswith("fj")
+    if weights.shape[0] != 3 * has_dp + 2 * C * has_fi + C * has_fj:
+        raise ValueError("weights: {} rows, local_input_feature {} of {} features has {}".format(weights.shape[0], local_input_feature, C,
+                                                                                              3 * has_dp + 2 * C * has_fi + C * has_fj))
+    if C_out % 4 != 0 or C_out > 1024:
+        raise NotImplementedError("pointwise_mlp: out_fdim {} (a multiple of 4 up to 1024)".format(C_out))
+    if K > 128:
+        raise NotImplementedError("pointwise_mlp: {} neighbours (at most 128)".format(K))
+    if gamma is not None and not is_training and (moving_mean is None or moving_variance is None):
+        raise ValueError("pointwise_mlp: is_training=False needs moving_mean and moving_variance")
+    from . import dense
+    o = 3 if has_dp else 0
+    w_pos = weights[:3].contiguous() if has_dp else None
+    center_term = None
+    if has_fi:
+        w_fi, w_df = weights[o:o + C], weights[o + C:o + 2 * C]
+        o += 2 * C
+        center_term = dense.linear(features, (w_fi - w_df).t())
+        w_n = w_df + weights[o:o + C] if has_fj else w_df
+    else:
+        w_n = weights[o:o + C]
+    neighbor_term = dense.linear(features, w_n.t())
+    bn_mode = 0 if gamma is None else (1 if is_training else 2)
+    return _PointWiseMLP.apply(query_points, support_points, neighbors_indices, center_term, neighbor_term.contiguous(), w_pos, gamma, beta, moving_mean,
+                               moving_variance, float(radius), bn_mode, _PW_ACTIVATIONS.get(activation_fn, 0), _PW_REDUCTIONS[reduction],
+                               float(bn_momentum), float(bn_eps))
+
+
+class PointWiseMLP(torch.nn.Module):
+    """the operator with its variables: fc_1/weights (xavier), fc_1/bn gamma, beta and the moving statistics (TF names)"""
+
+    def __init__(self, in_fdim, out_fdim, local_input_feature="dp_fj", fc_num=1, reduction="max", activation_fn="relu", bn=True, bn_momentum=0.98,
+                 bn_eps=1e-3):
+        super().__init__()
+        if fc_num != 1:
+            raise NotImplementedError("pointwisemlp.fc_num {}: only fc_num 1 is implemented (the fold of the FC layer holds for one layer)".format(fc_num))
+        if local_input_feature not in POINTWISE_MLP_INPUTS:
+            raise NotImplementedError("local_input_feature {} not supported in Point-wise MLP".format(local_input_feature))
+        d_in = 3 * local_input_feature.startswith("dp") + 2 * in_fdim * ("fi_df" in local_input_feature) + in_fdim * local_input_feature.endswith("fj")
+        self.local_input_feature, self.fc_num, self.reduction, self.activation_fn = local_input_feature, fc_num, reduction, activation_fn
+        self.bn_momentum, self.bn_eps = bn_momentum, bn_eps
+        self.weights = torch.nn.Parameter(torch.empty(d_in, out_fdim))
+        torch.nn.init.xavier_uniform_(self.weights)
+        if bn:
+            self.gamma = torch.nn.Parameter(torch.ones(out_fdim))
+            self.beta = torch.nn.Parameter(torch.zeros(out_fdim))
+            self.register_buffer("moving_mean", torch.zeros(out_fdim))
+            self.register_buffer("moving_variance", torch.ones(out_fdim))
+        else:
+            self.gamma = self.beta = self.moving_mean = self.moving_variance = None
+
+    def forward(self, query_points, support_points, neighbors_indices, features, radius):
+        return pointwise_mlp(query_points, support_points, neighbors_indices, features, radius, self.weights, self.gamma, self.beta, self.moving_mean,
+                             self.moving_variance, local_input_feature=self.local_input_feature, reduction=self.reduction,
+                             activation_fn=self.activation_fn, is_training=self.training, bn_momentum=self.bn_momentum, bn_eps=self.bn_eps,
+                             fc_num=self.fc_num)
 
 
 def ind_max_pool(x, inds):

@@ -457,6 +457,39 @@ int cbl_pospool_backward_csr(int n, int n0, int K, int C, const float* query_poi
                              const int* order_dst, const int* inv_start, const int* inv_src, float* grad_features,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* a14  PointWiseMLP  tensorflow/models/local_aggregation_operators.py:503-617 with fc_num 1 (one FC layer `fc_1` + batch norm + activation per pair, then
+ *   the mask and the reduction over K) without its (n,K,.) tensors.  One FC layer is linear in the concatenated blocks, so every local_input_feature
+ *   ('dp_fj' | 'fi_df' | 'dp_fi_df' | 'dp_fi_df_fj', :573-584) is, for the pair (i,k) with neighbour j = idx[i,k],
+ *       y[i,k,:] = ((s_j - q_i)/radius) @ w_pos (3,C_out)  +  center_term[idx[i,0]]  +  neighbor_term[j]
+ *   with the per-point products center_term = features @ (W_fi - W_df), neighbor_term = features @ (W_df + W_fj) (n0,C_out) made by the caller; a block a
+ *   mode lacks is NULL (w_pos, center_term).  Shadow neighbour (idx == n0): zero row of either term, point (0,0,0), mask 0.
+ *       out[i,:] = reduce_k  mask[i,k] * act( gamma * (y - mean) * invstd + beta )
+ *   bn_mode: 0 none | 1 batch statistics over all n*K pairs, shadow pairs included (biased variance; moving_mean / moving_var, when given, updated the TF way:
+ *            moving = moving * momentum + batch * (1 - momentum), biased variance) | 2 moving statistics.  Modes 1 and 2 leave the mean / invstd used in
+ *            save_mean / save_invstd (C_out), which the backward pass takes back.
+ *   activation: 0 none | 1 relu | 2 leaky_relu(0.2).   reduction: 0 'sum' | 1 'mean' (nn[i] as in AdaptiveWeight, *padding_num from cbl_index_max, :609-613)
+ *            | 2 'max' (reduce_max over activation * mask: a shadow pair counts as 0, :601-604).
+ *   C_out % 4 == 0, C_out <= 1024, 16-byte aligned rows, K <= 128 (CBL_ERR_UNSUPPORTED otherwise).  No float atomics: every output is written with plain
+ *   stores in a fixed summation order; no allocation or synchronisation inside a call.  workspace: cbl_pointwise_mlp_workspace_bytes (one size for both). */
+size_t cbl_pointwise_mlp_workspace_bytes(int n, int n0, int K, int C_out);
+int cbl_pointwise_mlp_forward(int n, int n0, int K, int C_out, const float* query_points, const float* support_points, const int* neighbors_indices,
+                              const float* center_term, const float* neighbor_term, const float* w_pos, float radius,
+                              int bn_mode, const float* gamma, const float* beta, float eps, float momentum, float* moving_mean, float* moving_var,
+                              int activation, int reduction, const int* padding_num, float* save_mean, float* save_invstd, float* out,
+                              void* workspace, size_t workspace_bytes, void* stream);
+/* gradients (any may be NULL), all WRITTEN: grad_center (n,C_out) per QUERY = sum_k dy[i,k,:] (the caller scatters it through idx[:,0] onto center_term's
+ * rows), grad_neighbor (n0,C_out) as a gather over the transposed table of neighbors_indices (cbl_neighbor_transpose with n0 targets, pairs p = i*K + k;
+ * needed only for grad_neighbor), grad_w_pos (3,C_out), grad_gamma / grad_beta (C_out).  dy is the gradient at y: through the reduction ('max' shared
+ * equally among the k that attain the maximum, like tf.reduce_max; `out` is the forward's result), the mask, the activation and the batch norm
+ * (bn_mode 1: dy = gamma * invstd * (dz - sum dz / N - xhat * sum(dz * xhat) / N), N = n*K, non-zero on shadow pairs too). */
+int cbl_pointwise_mlp_backward_csr(int n, int n0, int K, int C_out, const float* query_points, const float* support_points, const int* neighbors_indices,
+                                   const float* center_term, const float* neighbor_term, const float* w_pos, float radius,
+                                   int bn_mode, const float* gamma, const float* beta, const float* save_mean, const float* save_invstd,
+                                   int activation, int reduction, const int* padding_num, const float* out, const float* grad_out,
+                                   const int* order_dst, const int* inv_start, const int* inv_src,
+                                   float* grad_center, float* grad_neighbor, float* grad_w_pos, float* grad_gamma, float* grad_beta,
+                                   void* workspace, size_t workspace_bytes, void* stream);
+
 /* a4  PointTransformerLayer  pytorch/model/blocks.py:31-44, the C-wide part without its (n,K,C) tensors (C = 32 or 64, G = C/8):
  *   p1 (n,K,3) = ReLU(BN(Linear(3,3)(p_j - p_i)))  [computed by the caller: narrow],  p_r = Linear(3,C)(p1) = p1 @ W3C^T + b3C  [never stored]
  * attn_w2:  w2 (n,K,G) = Linear(C,G)( ReLU( BN_C( x_k[idx] - x_q + p_r ) ) )       (:39 and the first half of linear_w, :25-27)
