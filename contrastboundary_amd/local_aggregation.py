@@ -7,6 +7,7 @@
 Arguments keep the reference's names and order (query_points, support_points, neighbors_indices, features, ...); the
 trainable variables the TF code creates inside its variable scope (kernel weights, FC weight/bias) are explicit tensors.
 The batch-norm / activation / 1x1 convs that follow in the reference are dense layers outside this path (torch)."""
+import collections
 import ctypes
 
 import torch
@@ -373,24 +374,124 @@ class PointWiseMLP(torch.nn.Module):
                              fc_num=self.fc_num)
 
 
-def ind_max_pool(x, inds):
-    """basic_operators.py:155-172"""
-    _chk(x, torch.float32, "x"); _chk(inds, torch.int32, "inds")
+_NO_TABLE = "{}: no transposed neighbour table for more than 2^20 support points, and there is no scatter form"
+
+
+def _ind_max_pool_forward(x, inds):
+    """-> out (n2, d), scratch (d): the column minima of x as ordered keys, which the gradient reads"""
     n1, d = x.shape
     n2, k = inds.shape
     scratch = torch.empty(d, dtype=torch.int32, device=x.device)
     out = torch.empty((n2, d), dtype=torch.float32, device=x.device)
     _lib.check(_lib.lib().cbl_ind_max_pool(_i(n1), _i(n2), _i(k), _i(d), _lib.ptr(x), _lib.ptr(inds), _lib.ptr(scratch), _lib.ptr(out), _lib.stream_of(x)),
                "cbl_ind_max_pool")
-    return out
+    return out, scratch
 
 
-def ind_closest_pool(x, inds):
-    """basic_operators.py:175-192"""
-    _chk(x, torch.float32, "x"); _chk(inds, torch.int32, "inds")
+def _ind_closest_pool_forward(x, inds):
     n1, d = x.shape
     n2, k = inds.shape
     out = torch.empty((n2, d), dtype=torch.float32, device=x.device)
     _lib.check(_lib.lib().cbl_ind_closest_pool(_i(n1), _i(n2), _i(k), _i(d), _lib.ptr(x), _lib.ptr(inds), _lib.ptr(out), _lib.stream_of(x)),
                "cbl_ind_closest_pool")
     return out
+
+
+class _IndMaxPool(Function):
+    """cbl_ind_max_pool and its gradient csrc/index_pool.hip (cbl_amd.h): reduce_max / reduce_min share a gradient equally among ties"""
+
+    @staticmethod
+    def forward(ctx, x, inds):
+        out, scratch = _ind_max_pool_forward(x, inds)
+        ctx.save_for_backward(x, inds, scratch, out)                     # scratch is kept instead of discarded
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, inds, scratch, out = ctx.saved_tensors
+        n1, d = x.shape
+        n2, k = inds.shape
+        grad_out = grad_out.contiguous()
+        L = _lib.lib()
+        from . import pointops
+        # always the gather over the transposed table: the atomic cbl_grouping_backward does not guard shadow ids, and ties need the table's pairs anyway
+        tr = pointops.neighbor_transpose(inds, n1, build=True)
+        if tr is None:
+            raise NotImplementedError(_NO_TABLE.format("ind_max_pool"))
+        order, inv_start, inv_src = tr
+        grad_x = torch.empty_like(x)
+        ws = torch.empty(max(L.cbl_ind_max_pool_backward_workspace_bytes(_i(n1), _i(n2), _i(k), _i(d)), 1), dtype=torch.uint8, device=x.device)
+        _lib.check(L.cbl_ind_max_pool_backward_csr(_i(n1), _i(n2), _i(k), _i(d), _lib.ptr(x), _lib.ptr(inds), _lib.ptr(scratch), _lib.ptr(out), _lib.ptr(grad_out),
+                                                   _lib.ptr(order), _lib.ptr(inv_start), _lib.ptr(inv_src), _lib.ptr(grad_x), _lib.ptr(ws),
+                                                   ctypes.c_size_t(ws.numel()), _lib.stream_of(x)), "cbl_ind_max_pool_backward_csr")
+        return grad_x, None
+
+
+_first_columns = collections.OrderedDict()     # neighbour table -> (the table, its contiguous first column), the 16 most recent
+
+
+def _first_column(inds):
+    """inds[:, :1] as a tensor of its own, the SAME one for the same table from call to call: the transposed table built for it (neighbor_state's registry,
+    keyed by the tensor) is then found again by every later backward pass instead of being built per call"""
+    if inds.shape[1] == 1:
+        return inds
+    from . import neighbor_state
+    version = neighbor_state._version_of(inds)
+    if version < 0:
+        return inds[:, :1].contiguous()
+    key = (inds.data_ptr(), tuple(inds.shape), version, inds.device)
+    ent = _first_columns.get(key)
+    if ent is None:
+        ent = _first_columns[key] = (inds, inds[:, :1].contiguous())       # holding the table keeps its address from being reused under the key
+        while len(_first_columns) > 16:
+            _first_columns.popitem(last=False)
+    else:
+        _first_columns.move_to_end(key)
+    return ent[1]
+
+
+class _IndClosestPool(Function):
+    """cbl_ind_closest_pool; its gradient is the row scatter through the first column, as a gather over that column's transposed table"""
+
+    @staticmethod
+    def forward(ctx, x, inds):
+        out = _ind_closest_pool_forward(x, inds)
+        ctx.save_for_backward(_first_column(inds))
+        ctx.shape = tuple(x.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        inds0, = ctx.saved_tensors
+        n1, d = ctx.shape
+        grad_out = grad_out.contiguous()
+        from . import pointops
+        tr = pointops.neighbor_transpose(inds0, n1, build=True)          # shadow ids are in no segment: they receive nothing
+        if tr is None:
+            raise NotImplementedError(_NO_TABLE.format("ind_closest_pool"))
+        grad_x = torch.empty((n1, d), dtype=torch.float32, device=grad_out.device)
+        _lib.check(_lib.lib().cbl_grouping_backward_csr_rows(_i(n1), _i(d), _i(d), _i(0), _lib.ptr(grad_out), _lib.ptr(tr[0]), _lib.ptr(tr[1]), _lib.ptr(tr[2]),
+                                                             _lib.ptr(grad_x), _lib.stream_of(grad_out)), "cbl_grouping_backward_csr_rows")
+        return grad_x, None
+
+
+def ind_max_pool(x, inds):
+    """basic_operators.py:155-172, differentiable in x (ties of the maximum and of the shadow row's column minimum share the gradient equally, as
+    tf.reduce_max / tf.reduce_min do)"""
+    _chk(x, torch.float32, "x"); _chk(inds, torch.int32, "inds")
+    if not (x.requires_grad and torch.is_grad_enabled()):                # no gradient asked for: the forward entry alone, nothing kept
+        return _ind_max_pool_forward(x, inds)[0]
+    return _IndMaxPool.apply(x, inds)
+
+
+def ind_closest_pool(x, inds):
+    """basic_operators.py:175-192, differentiable in x"""
+    _chk(x, torch.float32, "x"); _chk(inds, torch.int32, "inds")
+    if not (x.requires_grad and torch.is_grad_enabled()):
+        return _ind_closest_pool_forward(x, inds)
+    return _IndClosestPool.apply(x, inds)
+
+
+def nearest_upsample(features, upsample_inds):
+    """nearest_upsample_block (models/heads/seg_head.py:13-28): features (n1, d) of the coarser layer, upsample_inds (n2, max_num) -> (n2, d)"""
+    return ind_closest_pool(features, upsample_inds)

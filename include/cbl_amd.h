@@ -697,6 +697,23 @@ int cbl_cross_entropy_backward(long long n, int k, const float* logits, const lo
  *   / the entry of the FIRST column (shadow row = 0) */
 int cbl_ind_max_pool(int n1, int n2, int k, int d, const float* x, const int* inds, unsigned* scratch_d, float* out, void* stream);
 int cbl_ind_closest_pool(int n1, int n2, int k, int d, const float* x, const int* inds, float* out, void* stream);
+/* The gradient of ind_max_pool, completing basic_operators.py:155-172 (x' = concat(x, reduce_min(x, 0)) :168, gather :170, reduce_max :172) under TensorFlow's
+ * gradient of reduce_max / reduce_min, which shares the incoming gradient EQUALLY among all tied entries (the shortcut of models/backbone/resnet.py's
+ * strided_bottleneck pools ReLU outputs: exact zeros tie everywhere).  With shadow[c] = min_s x[s,c], v[r,j,c] = x[inds[r,j],c] (shadow[c] for an id outside
+ * [0, n1)) and out[r,c] = max_j v[r,j,c]:
+ *   cnt[r,c] = #{j : v[r,j,c] == out[r,c]} (shadow entries and repeated ids count), w = grad_out / cnt, S[c] = sum_r w[r,c] * #{j shadow : shadow[c] == out[r,c]},
+ *   nmin[c] = #{s : x[s,c] == shadow[c]},   grad_x[s,c] = sum_{(r,j) : inds[r,j] == s} [x[s,c] == out[r,c]] * w[r,c] + [x[s,c] == shadow[c]] * S[c] / nmin[c].
+ * keymin_d: the forward's scratch_d as cbl_ind_max_pool left it (the column minima as ordered keys); out: the forward's result; order / inv_start / inv_src:
+ * cbl_neighbor_transpose of inds over n1 targets (order may be NULL; shadow ids are in no segment).  A gather: no float atomics, EVERY row of grad_x (n1,d) is
+ * written with plain stores (no pre-zeroing; a row nobody references gets its shadow share or exact zeros), S summed as fp64 per-workgroup partials in a fixed
+ * order: two calls give the same bits.  No allocation or synchronisation inside (capturable).  d % 4 == 0 with 16-byte aligned x / out / grad_out / grad_x takes
+ * the float4 kernels, anything else one channel per lane.  n2 == 0 writes zeros.  CBL_ERR_UNSUPPORTED: n2 * k >= 2^31.  Inputs finite.
+ * (ind_closest_pool's gradient — models/heads/seg_head.py:13-28, nearest_upsample_block — is grad_x[s,:] = sum_{r : inds[r,0] == s} grad_out[r,:]:
+ * cbl_grouping_backward_csr_rows over the transposed table of the contiguous first column; shadow entries receive nothing.) */
+size_t cbl_ind_max_pool_backward_workspace_bytes(int n1, int n2, int k, int d);
+int cbl_ind_max_pool_backward_csr(int n1, int n2, int k, int d, const float* x, const int* inds, const unsigned* keymin_d,
+                                  const float* out, const float* grad_out, const int* order, const int* inv_start, const int* inv_src,
+                                  float* grad_x, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * TF-side CPU ops of the reference (stacked clouds; here described by cumulative END offsets like the
