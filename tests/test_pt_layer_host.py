@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.pt_layer_oracle import EPS, PARAMS, knn, make, reference                # noqa: F401  (the layer's float64 formula and the scenes: other files take them from here)
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(ROOT, "contrastboundary_amd", "csrc", "pt_layer.hip")
@@ -31,57 +33,6 @@ def host():
 
 def P(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
-
-
-def knn(xyz, K):
-    d = ((xyz[:, None, :] - xyz[None, :, :]) ** 2).sum(-1)
-    return np.argsort(d, axis=1, kind="stable")[:, :K].astype(np.int32)
-
-
-def make(n, K, C, seed):
-    rng = np.random.default_rng(seed)
-    G = C // 8
-    f = lambda *s: rng.normal(size=s).astype(np.float32)
-    t = dict(xyz=rng.uniform(0, 1, (n, 3)).astype(np.float32), x_q=f(n, C), x_k=f(n, C), x_v=f(n, C),
-             Wp=f(3, 3) * 2, bp=f(3) * 0.1, gamma_p=rng.uniform(0.5, 1.5, 3).astype(np.float32), beta_p=f(3) * 0.2,
-             W3C=f(C, 3) * 0.5, b3C=f(C) * 0.1, gamma_c=rng.uniform(0.5, 1.5, C).astype(np.float32), beta_c=f(C) * 0.2,
-             Wa=f(G, C) * 0.3, ba=f(G) * 0.1, gamma_g=rng.uniform(0.5, 1.5, G).astype(np.float32), beta_g=f(G) * 0.2,
-             Wb=f(G, G) * 0.6, bb=f(G) * 0.1, g_out=f(n, C))
-    t["idx"] = knn(t["xyz"], K)
-    return t
-
-
-PARAMS = ["Wp", "bp", "gamma_p", "beta_p", "W3C", "b3C", "gamma_c", "beta_c", "Wa", "ba", "gamma_g", "beta_g", "Wb", "bb"]
-EPS = 1e-5
-
-
-def reference(t, K, C):
-    """blocks.py:31-44 behind the q/k/v Linear layers, float64, autograd"""
-    G = C // 8
-    T = {k: torch.tensor(v, dtype=torch.float64, requires_grad=(k in PARAMS or k in ("x_q", "x_k", "x_v"))) for k, v in t.items() if k != "idx"}
-    idx = torch.tensor(t["idx"].astype(np.int64))
-    n = idx.shape[0]
-
-    def bn(x, g, b):                                                  # train-mode BatchNorm1d over all rows
-        m = x.mean(0); v = x.var(0, unbiased=False)
-        return (x - m) / torch.sqrt(v + EPS) * g + b, m, v
-
-    p_r = T["xyz"][idx] - T["xyz"][:, None, :]
-    p0 = p_r @ T["Wp"].T + T["bp"]
-    y, mp, vp = bn(p0.reshape(n * K, 3), T["gamma_p"], T["beta_p"])
-    p1 = torch.relu(y).reshape(n, K, 3)
-    pe = p1 @ T["W3C"].T + T["b3C"]
-    w = T["x_k"][idx] - T["x_q"][:, None, :] + pe
-    y, mc, vc = bn(w.reshape(n * K, C), T["gamma_c"], T["beta_c"])
-    w2 = torch.relu(y) @ T["Wa"].T + T["ba"]
-    y, mg, vg = bn(w2, T["gamma_g"], T["beta_g"])
-    logits = (torch.relu(y) @ T["Wb"].T + T["bb"]).reshape(n, K, G)
-    a = torch.softmax(logits, dim=1)
-    out = ((T["x_v"][idx] + pe).view(n, K, 8, G) * a.unsqueeze(2)).sum(1).view(n, C)
-    (out * T["g_out"]).sum().backward()
-    grads = {k: T[k].grad.numpy() for k in PARAMS + ["x_q", "x_k", "x_v"]}
-    stats = dict(mean=[mp, mc, mg], var=[vp, vc, vg])
-    return out.detach().numpy(), grads, dict(p1=p1.detach().numpy(), w2=w2.detach().reshape(n, K, G).numpy(), a=a.detach().numpy()), stats
 
 
 def transpose_table(idx, order):
