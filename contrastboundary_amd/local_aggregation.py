@@ -1,6 +1,6 @@
 """Host mirror of the TF-side local aggregation operators (value semantics of the TF1 graph code):
     kpconv (PseudoGrid)   /root/reference/tensorflow/models/local_aggregation_operators.py:620-746
-    adaptive_weight       ...:316-500 (shipped options, config/s3dis/adapt.yaml:19-26)
+    adaptive_weight       ...:316-500 (fc_num 1; the shipped options, config/s3dis/adapt.yaml:19-26, on kernels of their own)
     pospool               ...:15-250
     pointwise_mlp         ...:503-617 (fc_num 1; its batch norm and activation sit INSIDE the per-pair MLP, before the reduction: part of the kernels)
     ind_max_pool / ind_closest_pool   /root/reference/tensorflow/models/basic_operators.py:155-192
@@ -145,15 +145,170 @@ class _AdaptiveWeight(Function):
         return None, None, None, gf, gw, gb, None, None
 
 
-def adaptive_weight(query_points, support_points, neighbors_indices, features, radius, fc_weight, fc_bias, reduction="mean"):
-    """AdaptiveWeight aggregation_feature (n, C) before batch norm / activation, shipped options (see module docstring)."""
+ADAPTIVE_WEIGHT_INPUTS = ("dp", "df", "dp_df", "fj", "dp_fj", "fi_df", "dp_fi_df")
+_AW_SOFTMAX = {None: 0, False: 0, "dense": 1, "sparse": 1, "mask": 1, "unmask": 2}
+_AW_REDUCTIONS = {"sum": 0, "mean": 1, "avg": 1, "max": 2}
+_NO_TABLE = "{}: no transposed neighbour table for more than 2^20 support points, and there is no scatter form"
+
+
+def _aw_d_in(local_input_feature, in_fdim):
+    blocks = local_input_feature.split("_")
+    return 3 * ("dp" in blocks) + in_fdim * sum(b in blocks for b in ("fi", "df", "fj"))
+
+
+def _aw_options(local_input_feature, shared_channels, weight_softmax, reduction, in_fdim):
+    """-> S = min(shared_channels, in_fdim); refuses what the kernels (and for 'rscnn' / 'gac' this mirror) do not cover, naming the option"""
+    if local_input_feature not in ADAPTIVE_WEIGHT_INPUTS:
+        raise NotImplementedError("local_input_feature {} not supported in AdaptiveWeight (one of {})".format(local_input_feature, ", ".join(ADAPTIVE_WEIGHT_INPUTS)))
+    if weight_softmax not in _AW_SOFTMAX:
+        raise NotImplementedError("weight_softmax {!r} not supported in AdaptiveWeight (False, 'dense', 'sparse', 'mask' or 'unmask')".format(weight_softmax))
+    if reduction not in _AW_REDUCTIONS:
+        raise NotImplementedError("Reduction {} not supported in AdaptiveWeight".format(reduction))
+    S = min(int(shared_channels), in_fdim)
+    if S < 1 or in_fdim % S != 0:
+        raise NotImplementedError("shared_channels {}: {} features do not divide into groups of it (the reference's reshape fails as well)".format(shared_channels, in_fdim))
+    if S not in (1, 2, 4) and S % 4 != 0:
+        raise NotImplementedError("shared_channels {}: 1, 2, 4 or a multiple of 4".format(shared_channels))
+    return S
+
+
+class _AdaptiveWeightGeneral(Function):
+    """the two entries of csrc/adaptive_weight_general.hip around the folded per-point terms (cbl_amd.h, a14 AdaptiveWeight, every option)"""
+
+    @staticmethod
+    def forward(ctx, query_points, support_points, neighbors_indices, features, center_term, neighbor_term, w_pos, bias, radius, softmax, red):
+        n, K = neighbors_indices.shape
+        n0, C = features.shape
+        M = bias.shape[0]
+        L = _lib.lib()
+        dev = features.device
+        st = _lib.stream_of(features)
+        pad = torch.empty(1, dtype=torch.int32, device=dev)
+        if red == 1:
+            _lib.check(L.cbl_index_max(ctypes.c_longlong(n * K), _lib.ptr(neighbors_indices), _lib.ptr(pad), st), "cbl_index_max")
+        out = torch.empty((n, C), dtype=torch.float32, device=dev)
+        _lib.check(L.cbl_adaptive_weight_general_forward(_i(n), _i(n0), _i(K), _i(C), _i(M), _lib.ptr(query_points), _lib.ptr(support_points),
+                                                         _lib.ptr(neighbors_indices), _lib.ptr(features), _lib.ptr(center_term), _lib.ptr(neighbor_term),
+                                                         _lib.ptr(w_pos), _lib.ptr(bias), _f(radius), _i(softmax), _i(red), _lib.ptr(pad), _lib.ptr(out),
+                                                         None, ctypes.c_size_t(0), st), "cbl_adaptive_weight_general_forward")
+        ctx.save_for_backward(query_points, support_points, neighbors_indices, features, center_term, neighbor_term, w_pos, bias, pad, out)
+        ctx.cfg = (radius, softmax, red)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        q, s, idx, f, cen, nbr, wp, bias, pad, out = ctx.saved_tensors
+        radius, softmax, red = ctx.cfg
+        n, K = idx.shape
+        n0, C = f.shape
+        M = bias.shape[0]
+        grad_out = grad_out.contiguous()
+        L = _lib.lib()
+        dev = f.device
+        st = _lib.stream_of(f)
+        from . import pointops
+        need = ctx.needs_input_grad
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        gf = new(n0, C) if need[3] else None
+        gc = new(n, M) if cen is not None and need[4] else None
+        gn = new(n0, M) if nbr is not None and need[5] else None
+        gwp = new(3, M) if wp is not None and need[6] else None
+        gb = new(M) if need[7] else None
+        order = inv_start = inv_src = None
+        if gf is not None or gn is not None:
+            tr = pointops.neighbor_transpose(idx, n0, build=True)
+            if tr is None:
+                raise NotImplementedError(_NO_TABLE.format("adaptive_weight"))
+            order, inv_start, inv_src = tr
+        ws = torch.empty(max(L.cbl_adaptive_weight_general_workspace_bytes(_i(n), _i(n0), _i(K), _i(C), _i(M)), 1), dtype=torch.uint8, device=dev)
+        _lib.check(L.cbl_adaptive_weight_general_backward_csr(_i(n), _i(n0), _i(K), _i(C), _i(M), _lib.ptr(q), _lib.ptr(s), _lib.ptr(idx), _lib.ptr(f),
+                                                              _lib.ptr(cen), _lib.ptr(nbr), _lib.ptr(wp), _lib.ptr(bias), _f(radius), _i(softmax), _i(red),
+                                                              _lib.ptr(pad), _lib.ptr(out), _lib.ptr(grad_out), _lib.ptr(order), _lib.ptr(inv_start),
+                                                              _lib.ptr(inv_src), _lib.ptr(gf), _lib.ptr(gc), _lib.ptr(gn), _lib.ptr(gwp), _lib.ptr(gb),
+                                                              _lib.ptr(ws), ctypes.c_size_t(ws.numel()), st), "cbl_adaptive_weight_general_backward_csr")
+        gcen = None
+        if gc is not None:
+            # per-query rows onto the centre rows they came from (shadow_features[idx[:, 0]]): the row scatter as a gather over the table of that one column
+            tr0 = pointops.neighbor_transpose(idx[:, :1].contiguous(), n0, build=True)
+            if tr0 is None:
+                raise NotImplementedError(_NO_TABLE.format("adaptive_weight"))
+            gcen = new(n0, M)
+            _lib.check(L.cbl_grouping_backward_csr_rows(_i(n0), _i(M), _i(M), _i(0), _lib.ptr(gc), _lib.ptr(tr0[0]), _lib.ptr(tr0[1]), _lib.ptr(tr0[2]),
+                                                        _lib.ptr(gcen), st), "cbl_grouping_backward_csr_rows")
+        return None, None, None, gf, gcen, gn, gwp, gb, None, None, None
+
+
+def adaptive_weight(query_points, support_points, neighbors_indices, features, radius, fc_weight, fc_bias, reduction="mean", *,
+                    local_input_feature="dp", shared_channels=1, weight_softmax=False):
+    """AdaptiveWeight aggregation_feature (n, C) before batch norm / activation / output_conv (tensorflow/models/local_aggregation_operators.py:316-480;
+    options as config.adaptive_weight.*) with fc_num 1.  fc_weight: the TF variable fc_1/weights (D_in, M), M = C / min(shared_channels, C), rows in the
+    concatenation order of :386-401; fc_bias (M).
+    The shipped options ('dp', shared_channels 1, no softmax, sum / mean) run the kernels specialised for them.  Everything else: one FC layer is linear in
+    the concatenated blocks, y = dp @ W_p + (f @ (W_fi - W_df))[idx[:, 0]] + (f @ (W_df + W_fj))[idx] + bias — the two per-point products are dense layers
+    here (autograd carries the fold and the weight gradient), the per-pair part is csrc/adaptive_weight_general.hip.
+    weight_softmax 'dense' / 'sparse' / 'mask' are one masked softmax over the real neighbours; for a query without any real neighbour it gives zero
+    weights (so do the reference's 'sparse' and, in effect, 'dense'; its 'mask' divides 0 by 0 there and yields NaN — such a query does not occur in its
+    pipelines, where column 0 is the point itself)."""
+    S = _aw_options(local_input_feature, shared_channels, weight_softmax, reduction, features.shape[1])
+    C = features.shape[1]
+    M = C // S
+    if tuple(fc_weight.shape) != (_aw_d_in(local_input_feature, C), M):
+        raise ValueError("fc_weight: shape {}, local_input_feature {} of {} features with shared_channels {} has ({}, {})".format(
+            tuple(fc_weight.shape), local_input_feature, C, shared_channels, _aw_d_in(local_input_feature, C), M))
     _chk(query_points, torch.float32, "query_points"); _chk(support_points, torch.float32, "support_points")
     _chk(neighbors_indices, torch.int32, "neighbors_indices"); _chk(features, torch.float32, "features")
     _chk(fc_weight, torch.float32, "fc_weight"); _chk(fc_bias, torch.float32, "fc_bias")
-    if reduction not in ("mean", "avg", "sum"):
-        raise NotImplementedError(f"Reduction {reduction} not supported in the fused AdaptiveWeight")
-    return _AdaptiveWeight.apply(query_points, support_points, neighbors_indices, features, fc_weight, fc_bias, float(radius),
-                                 1 if reduction in ("mean", "avg") else 0)
+    softmax, red = _AW_SOFTMAX[weight_softmax], _AW_REDUCTIONS[reduction]
+    if local_input_feature == "dp" and S == 1 and softmax == 0 and red != 2:
+        return _AdaptiveWeight.apply(query_points, support_points, neighbors_indices, features, fc_weight, fc_bias, float(radius), red)
+    if C % 4 != 0 or C > 1152:
+        raise NotImplementedError("adaptive_weight: {} features (a multiple of 4 up to 1152)".format(C))
+    if neighbors_indices.shape[1] > 128:
+        raise NotImplementedError("adaptive_weight: {} neighbours (at most 128)".format(neighbors_indices.shape[1]))
+    from . import dense
+    blocks, o = {}, 0
+    for name in local_input_feature.split("_"):
+        rows = 3 if name == "dp" else C
+        blocks[name] = fc_weight[o:o + rows]
+        o += rows
+    w_pos = blocks["dp"].contiguous() if "dp" in blocks else None
+    center_term = neighbor_term = None
+    if "fi" in blocks or "df" in blocks:
+        w_c = blocks["fi"] - blocks["df"] if "fi" in blocks else -blocks["df"]
+        center_term = dense.linear(features, w_c.t()).contiguous()
+    if "df" in blocks or "fj" in blocks:
+        w_n = blocks["df"] if "df" in blocks else blocks["fj"]              # (no mode of :386-401 has both)
+        neighbor_term = dense.linear(features, w_n.t()).contiguous()
+    return _AdaptiveWeightGeneral.apply(query_points, support_points, neighbors_indices, features, center_term, neighbor_term, w_pos, fc_bias, float(radius),
+                                        softmax, red)
+
+
+def _fan_in_init_(weights):
+    """tf.contrib.layers.variance_scaling_initializer(factor=1.0, mode='FAN_IN', uniform=False): a normal of standard deviation sqrt(1.3 / fan_in)
+    truncated at two standard deviations; fan_in = the rows of a TF (in, out) weight"""
+    std = (1.3 / weights.shape[0]) ** 0.5
+    with torch.no_grad():
+        return torch.nn.init.trunc_normal_(weights, 0.0, std, -2 * std, 2 * std)
+
+
+class AdaptiveWeight(torch.nn.Module):
+    """the operator with its variables: fc_1/weights (D_in, M) drawn as the reference's 'fan_in' initializer does (basic_operators.py:120-121), fc_1/biases zero"""
+
+    def __init__(self, in_fdim, local_input_feature="dp", shared_channels=1, fc_num=1, weight_softmax=False, reduction="mean"):
+        super().__init__()
+        if fc_num != 1:
+            raise NotImplementedError("adaptive_weight.fc_num {}: only fc_num 1 is implemented (the fold of the FC layer holds for one layer)".format(fc_num))
+        S = _aw_options(local_input_feature, shared_channels, weight_softmax, reduction, in_fdim)
+        d_in, M = _aw_d_in(local_input_feature, in_fdim), in_fdim // S
+        self.local_input_feature, self.shared_channels, self.fc_num = local_input_feature, shared_channels, fc_num
+        self.weight_softmax, self.reduction = weight_softmax, reduction
+        self.weights = torch.nn.Parameter(torch.empty(d_in, M))
+        _fan_in_init_(self.weights)
+        self.biases = torch.nn.Parameter(torch.zeros(M))
+
+    def forward(self, query_points, support_points, neighbors_indices, features, radius):
+        return adaptive_weight(query_points, support_points, neighbors_indices, features, radius, self.weights, self.biases, self.reduction,
+                               local_input_feature=self.local_input_feature, shared_channels=self.shared_channels, weight_softmax=self.weight_softmax)
 
 
 POSPOOL_EMBEDDINGS = {"one": 0, "xyz": 1, "distance": 2, "exp_-d": 3, "direction_exp_-d": 4, "direction_d": 5, "sin_cos": 6,
@@ -372,9 +527,6 @@ class PointWiseMLP(torch.nn.Module):
                              self.moving_variance, local_input_feature=self.local_input_feature, reduction=self.reduction,
                              activation_fn=self.activation_fn, is_training=self.training, bn_momentum=self.bn_momentum, bn_eps=self.bn_eps,
                              fc_num=self.fc_num)
-
-
-_NO_TABLE = "{}: no transposed neighbour table for more than 2^20 support points, and there is no scatter form"
 
 
 def _ind_max_pool_forward(x, inds):

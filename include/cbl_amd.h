@@ -435,6 +435,39 @@ int cbl_adaptive_weight_backward_csr(int n, int n0, int K, int C, const float* q
                                      int reduction_mean, const float* grad_out, const int* order_dst, const int* inv_start, const int* inv_src,
                                      float* grad_features, float* grad_fc_weight, float* grad_fc_bias, void* workspace, size_t workspace_bytes, void* stream);
 
+/* a14  AdaptiveWeight, every option of fc_num 1  tensorflow/models/local_aggregation_operators.py:316-500: local_input_feature 'dp' | 'df' | 'dp_df' | 'fj' |
+ *   'dp_fj' | 'fi_df' | 'dp_fi_df' (:386-401), shared_channels S (M = C / S weight groups, channel c in group c / S, :455-459), weight_softmax (:432-453),
+ *   reduction sum | mean | max (:461-480), without its (n,K,.) tensors.  `fc_1` (:426-430, with bias) is linear in the concatenated blocks, so for the
+ *   pair (i,k) with neighbour j = idx[i,k]
+ *       y[i,k,m] = ((s_j - q_i)/radius) . w_pos[:,m]  +  center_term[idx[i,0]][m]  +  neighbor_term[j][m]  +  bias[m]
+ *   with the per-point products center_term = features @ (W_fi - W_df), neighbor_term = features @ (W_df + W_fj) (n0,M) made by the caller; a block a mode
+ *   lacks is NULL (w_pos, center_term, neighbor_term).  Shadow neighbour (idx == n0): zero rows, point (0,0,0).
+ *       w = y (softmax 0) | softmax over the k of the real pairs, 0 on shadow pairs, all 0 for a query without a real pair (1: 'dense' / 'sparse' / 'mask')
+ *           | softmax over all K pairs (2: 'unmask')
+ *       out[i,c] = sum_k w[i,k,c/S] f_j[c]  (0 'sum') | that / nn[i] (1 'mean', nn and *padding_num as for cbl_adaptive_weight_forward)
+ *                | max_k (w f_j[c], -65535 on a shadow pair) (2 'max')
+ *   C % 4 == 0, C <= 1152, 16-byte aligned rows, K <= 128, C % M == 0 and S = C / M in {1, 2, 4} or a multiple of 4 (CBL_ERR_UNSUPPORTED otherwise).
+ *   No float atomics: every output is written with plain stores in a fixed summation order; no allocation or synchronisation inside a call.
+ *   workspace: cbl_adaptive_weight_general_workspace_bytes (one size for both calls, 0 = unsupported; the forward call does not touch it). */
+size_t cbl_adaptive_weight_general_workspace_bytes(int n, int n0, int K, int C, int M);
+int cbl_adaptive_weight_general_forward(int n, int n0, int K, int C, int M, const float* query_points, const float* support_points,
+                                        const int* neighbors_indices, const float* features, const float* center_term, const float* neighbor_term,
+                                        const float* w_pos, const float* bias, float radius, int softmax, int reduction, const int* padding_num,
+                                        float* out, void* workspace, size_t workspace_bytes, void* stream);
+/* gradients (any may be NULL), all WRITTEN.  With da[i,k,c] = grad_out[i,c] * (1 | 1/nn[i] | [k attains the maximum] / #ties) on real pairs (`out` is the
+ * forward's result, ties share like tf.reduce_max), dw[i,k,m] = sum_{c in m} da f_j[c] and dy = dw (softmax 0) | w (dw - sum_k' w dw) over the softmax's domain:
+ *   grad_features_value (n0,C) = sum over the pairs -> j of da * w      grad_neighbor (n0,M) = sum over the pairs -> j of dy
+ *       (both as a gather over the transposed table of neighbors_indices: cbl_neighbor_transpose with n0 targets, pairs p = i*K + k; needed for these two only)
+ *   grad_center (n,M) per QUERY = sum_k dy (the caller scatters it through idx[:,0] onto center_term's rows)
+ *   grad_w_pos (3,M) = sum dp^T dy      grad_bias (M) = sum dy
+ * Under a softmax sum_k dy is 0 by its shift invariance: grad_center and grad_bias are written as exact zeros there. */
+int cbl_adaptive_weight_general_backward_csr(int n, int n0, int K, int C, int M, const float* query_points, const float* support_points,
+                                             const int* neighbors_indices, const float* features, const float* center_term, const float* neighbor_term,
+                                             const float* w_pos, const float* bias, float radius, int softmax, int reduction, const int* padding_num,
+                                             const float* out, const float* grad_out, const int* order_dst, const int* inv_start, const int* inv_src,
+                                             float* grad_features_value, float* grad_center, float* grad_neighbor, float* grad_w_pos, float* grad_bias,
+                                             void* workspace, size_t workspace_bytes, void* stream);
+
 /* a14  PosPool  tensorflow/models/local_aggregation_operators.py:15-250 (shipped: config/s3dis/pospool.yaml:20-23 'sin_cos' + 'mean')
  *   out[p,c] = reduce_k geo[p,k,c/(C/mid)] * features[nbr(p,k),c]   (before pool_bn / activation / output_conv, :251-270)
  *   position_embedding: 0 'one' | 1 'xyz' | 2 'distance' | 3 'exp_-d' | 4 'direction_exp_-d' | 5 'direction_d' | 6 'sin_cos' |
