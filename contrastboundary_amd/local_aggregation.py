@@ -1,6 +1,6 @@
 """Host mirror of the TF-side local aggregation operators (value semantics of the TF1 graph code):
     kpconv (PseudoGrid)   /root/reference/tensorflow/models/local_aggregation_operators.py:620-746
-    adaptive_weight       ...:316-500 (fc_num 1; the shipped options, config/s3dis/adapt.yaml:19-26, on kernels of their own)
+    adaptive_weight       ...:316-500 (fc_num 1, 2, 3; the shipped options, config/s3dis/adapt.yaml:19-26, on kernels of their own)
     pospool               ...:15-250
     pointwise_mlp         ...:503-617 (fc_num 1; its batch norm and activation sit INSIDE the per-pair MLP, before the reduction: part of the kernels)
     ind_max_pool / ind_closest_pool   /root/reference/tensorflow/models/basic_operators.py:155-192
@@ -238,17 +238,107 @@ class _AdaptiveWeightGeneral(Function):
         return None, None, None, gf, gcen, gn, gwp, gb, None, None, None
 
 
+class _AdaptiveWeightMLP(Function):
+    """the two entries of csrc/adaptive_weight_mlp.hip around the folded per-point terms (cbl_amd.h, a14 AdaptiveWeight with fc_num 2 and 3);
+    hidden_w (layers, M, M) / hidden_b (layers, M): the layers behind the first, stacked"""
+
+    @staticmethod
+    def forward(ctx, query_points, support_points, neighbors_indices, features, center_term, neighbor_term, w_pos, bias, hidden_w, hidden_b, radius, softmax,
+                red, act):
+        n, K = neighbors_indices.shape
+        n0, C = features.shape
+        M, layers = bias.shape[0], hidden_w.shape[0]
+        L = _lib.lib()
+        dev = features.device
+        st = _lib.stream_of(features)
+        pad = torch.empty(1, dtype=torch.int32, device=dev)
+        if red == 1:
+            _lib.check(L.cbl_index_max(ctypes.c_longlong(n * K), _lib.ptr(neighbors_indices), _lib.ptr(pad), st), "cbl_index_max")
+        out = torch.empty((n, C), dtype=torch.float32, device=dev)
+        _lib.check(L.cbl_adaptive_weight_mlp_forward(_i(n), _i(n0), _i(K), _i(C), _i(M), _lib.ptr(query_points), _lib.ptr(support_points),
+                                                     _lib.ptr(neighbors_indices), _lib.ptr(features), _lib.ptr(center_term), _lib.ptr(neighbor_term),
+                                                     _lib.ptr(w_pos), _lib.ptr(bias), _i(layers), _lib.ptr(hidden_w), _lib.ptr(hidden_b), _i(act), _f(radius),
+                                                     _i(softmax), _i(red), _lib.ptr(pad), _lib.ptr(out), None, ctypes.c_size_t(0), st),
+                   "cbl_adaptive_weight_mlp_forward")
+        ctx.save_for_backward(query_points, support_points, neighbors_indices, features, center_term, neighbor_term, w_pos, bias, hidden_w, hidden_b, pad, out)
+        ctx.cfg = (radius, softmax, red, act)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        q, s, idx, f, cen, nbr, wp, bias, hw, hb, pad, out = ctx.saved_tensors
+        radius, softmax, red, act = ctx.cfg
+        n, K = idx.shape
+        n0, C = f.shape
+        M, layers = bias.shape[0], hw.shape[0]
+        grad_out = grad_out.contiguous()
+        L = _lib.lib()
+        dev = f.device
+        st = _lib.stream_of(f)
+        from . import pointops
+        need = ctx.needs_input_grad
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        gf = new(n0, C) if need[3] else None
+        gc = new(n, M) if cen is not None and need[4] else None
+        gn = new(n0, M) if nbr is not None and need[5] else None
+        gwp = new(3, M) if wp is not None and need[6] else None
+        gb = new(M) if need[7] else None
+        ghw = new(layers, M, M) if need[8] else None
+        ghb = new(layers, M) if need[9] else None
+        order = inv_start = inv_src = None
+        if gf is not None or gn is not None:
+            tr = pointops.neighbor_transpose(idx, n0, build=True)
+            if tr is None:
+                raise NotImplementedError(_NO_TABLE.format("adaptive_weight"))
+            order, inv_start, inv_src = tr
+        ws = torch.empty(max(L.cbl_adaptive_weight_mlp_workspace_bytes(_i(n), _i(n0), _i(K), _i(C), _i(M), _i(layers)), 1), dtype=torch.uint8, device=dev)
+        _lib.check(L.cbl_adaptive_weight_mlp_backward_csr(_i(n), _i(n0), _i(K), _i(C), _i(M), _lib.ptr(q), _lib.ptr(s), _lib.ptr(idx), _lib.ptr(f),
+                                                          _lib.ptr(cen), _lib.ptr(nbr), _lib.ptr(wp), _lib.ptr(bias), _i(layers), _lib.ptr(hw), _lib.ptr(hb),
+                                                          _i(act), _f(radius), _i(softmax), _i(red), _lib.ptr(pad), _lib.ptr(out), _lib.ptr(grad_out),
+                                                          _lib.ptr(order), _lib.ptr(inv_start), _lib.ptr(inv_src), _lib.ptr(gf), _lib.ptr(gc), _lib.ptr(gn),
+                                                          _lib.ptr(gwp), _lib.ptr(gb), _lib.ptr(ghw), _lib.ptr(ghb), _lib.ptr(ws),
+                                                          ctypes.c_size_t(ws.numel()), st), "cbl_adaptive_weight_mlp_backward_csr")
+        gcen = None
+        if gc is not None:
+            # per-query rows onto the centre rows they came from, as _AdaptiveWeightGeneral does
+            tr0 = pointops.neighbor_transpose(idx[:, :1].contiguous(), n0, build=True)
+            if tr0 is None:
+                raise NotImplementedError(_NO_TABLE.format("adaptive_weight"))
+            gcen = new(n0, M)
+            _lib.check(L.cbl_grouping_backward_csr_rows(_i(n0), _i(M), _i(M), _i(0), _lib.ptr(gc), _lib.ptr(tr0[0]), _lib.ptr(tr0[1]), _lib.ptr(tr0[2]),
+                                                        _lib.ptr(gcen), st), "cbl_grouping_backward_csr_rows")
+        return None, None, None, gf, gcen, gn, gwp, gb, ghw, ghb, None, None, None, None
+
+
+_AW_MLP_M = (16, 144)          # the widths csrc/adaptive_weight_mlp.hip takes (one matrix tile .. the ConvNet's stage-2 width)
+
+
+def _aw_mlp_limits(fc_num, M, K=None):
+    """refuses the depths and widths the per-pair MLP kernels do not cover, naming fc_num"""
+    if fc_num > 3:
+        raise NotImplementedError("adaptive_weight.fc_num {}: fc_num 1, 2 and 3 are implemented".format(fc_num))
+    if not _AW_MLP_M[0] <= M <= _AW_MLP_M[1]:
+        raise NotImplementedError("adaptive_weight.fc_num {}: only fc_num 1 is implemented for {} weight groups (the per-pair MLP kernels take {} to {})".format(
+            fc_num, M, *_AW_MLP_M))
+    if K is not None and (K > 128 or (K > 48 and M > 64)):
+        raise NotImplementedError("adaptive_weight.fc_num {}: {} neighbours with {} weight groups (at most 48, or 128 up to 64 groups)".format(fc_num, K, M))
+
+
 def adaptive_weight(query_points, support_points, neighbors_indices, features, radius, fc_weight, fc_bias, reduction="mean", *,
-                    local_input_feature="dp", shared_channels=1, weight_softmax=False):
+                    local_input_feature="dp", shared_channels=1, weight_softmax=False, fc_hidden=(), activation_fn="relu"):
     """AdaptiveWeight aggregation_feature (n, C) before batch norm / activation / output_conv (tensorflow/models/local_aggregation_operators.py:316-480;
-    options as config.adaptive_weight.*) with fc_num 1.  fc_weight: the TF variable fc_1/weights (D_in, M), M = C / min(shared_channels, C), rows in the
+    options as config.adaptive_weight.*) with fc_num 1 + len(fc_hidden) (1, 2 or 3).  fc_weight: the TF variable fc_1/weights (D_in, M), M = C / min(shared_channels, C), rows in the
     concatenation order of :386-401; fc_bias (M).
     The shipped options ('dp', shared_channels 1, no softmax, sum / mean) run the kernels specialised for them.  Everything else: one FC layer is linear in
     the concatenated blocks, y = dp @ W_p + (f @ (W_fi - W_df))[idx[:, 0]] + (f @ (W_df + W_fj))[idx] + bias — the two per-point products are dense layers
     here (autograd carries the fold and the weight gradient), the per-pair part is csrc/adaptive_weight_general.hip.
     weight_softmax 'dense' / 'sparse' / 'mask' are one masked softmax over the real neighbours; for a query without any real neighbour it gives zero
     weights (so do the reference's 'sparse' and, in effect, 'dense'; its 'mask' divides 0 by 0 there and yields NaN — such a query does not occur in its
-    pipelines, where column 0 is the point itself)."""
+    pipelines, where column 0 is the point itself).
+    fc_hidden: (weight (M, M), bias (M)) of every layer behind the first, in order (:419-430; TF's (in, out) weights).  The first layer is followed by
+    activation_fn ('relu', 'leaky_relu' with alpha 0.2, anything else the identity: basic_operators.py:285-289), so are the layers between; the last has
+    none.  The first layer keeps its fold and its dense products; the per-pair MLP is csrc/adaptive_weight_mlp.hip (16 <= M <= 144; K <= 48, or <= 128 up
+    to M = 64).  With fc_hidden empty, activation_fn is unused and the call is fc_num 1's."""
     S = _aw_options(local_input_feature, shared_channels, weight_softmax, reduction, features.shape[1])
     C = features.shape[1]
     M = C // S
@@ -259,7 +349,15 @@ def adaptive_weight(query_points, support_points, neighbors_indices, features, r
     _chk(neighbors_indices, torch.int32, "neighbors_indices"); _chk(features, torch.float32, "features")
     _chk(fc_weight, torch.float32, "fc_weight"); _chk(fc_bias, torch.float32, "fc_bias")
     softmax, red = _AW_SOFTMAX[weight_softmax], _AW_REDUCTIONS[reduction]
-    if local_input_feature == "dp" and S == 1 and softmax == 0 and red != 2:
+    fc_hidden = tuple(fc_hidden)
+    if fc_hidden:
+        _aw_mlp_limits(1 + len(fc_hidden), M, neighbors_indices.shape[1])
+        for l, (w, b) in enumerate(fc_hidden, 1):
+            _chk(w, torch.float32, "fc_hidden[{}] weight".format(l - 1)); _chk(b, torch.float32, "fc_hidden[{}] bias".format(l - 1))
+            if tuple(w.shape) != (M, M) or tuple(b.shape) != (M,):
+                raise ValueError("fc_hidden[{}]: shapes {} and {}, a layer of {} weight groups has ({}, {}) and ({},)".format(
+                    l - 1, tuple(w.shape), tuple(b.shape), M, M, M, M))
+    if not fc_hidden and local_input_feature == "dp" and S == 1 and softmax == 0 and red != 2:
         return _AdaptiveWeight.apply(query_points, support_points, neighbors_indices, features, fc_weight, fc_bias, float(radius), red)
     if C % 4 != 0 or C > 1152:
         raise NotImplementedError("adaptive_weight: {} features (a multiple of 4 up to 1152)".format(C))
@@ -279,6 +377,10 @@ def adaptive_weight(query_points, support_points, neighbors_indices, features, r
     if "df" in blocks or "fj" in blocks:
         w_n = blocks["df"] if "df" in blocks else blocks["fj"]              # (no mode of :386-401 has both)
         neighbor_term = dense.linear(features, w_n.t()).contiguous()
+    if fc_hidden:
+        return _AdaptiveWeightMLP.apply(query_points, support_points, neighbors_indices, features, center_term, neighbor_term, w_pos, fc_bias,
+                                        torch.stack([w for w, _ in fc_hidden]), torch.stack([b for _, b in fc_hidden]), float(radius), softmax, red,
+                                        _PW_ACTIVATIONS.get(activation_fn, 0))
     return _AdaptiveWeightGeneral.apply(query_points, support_points, neighbors_indices, features, center_term, neighbor_term, w_pos, fc_bias, float(radius),
                                         softmax, red)
 
@@ -292,23 +394,42 @@ def _fan_in_init_(weights):
 
 
 class AdaptiveWeight(torch.nn.Module):
-    """the operator with its variables: fc_1/weights (D_in, M) drawn as the reference's 'fan_in' initializer does (basic_operators.py:120-121), fc_1/biases zero"""
+    """the operator with its variables, drawn as the reference's 'fan_in' initializer does (basic_operators.py:120-121) with zero biases: `weights` (D_in, M) /
+    `biases` of the first layer, and for fc_num 2 and 3 `weights_1`, `biases_1` (, `weights_2`, `biases_2`) (M, M) / (M) of the layers behind it (:419-430)"""
 
-    def __init__(self, in_fdim, local_input_feature="dp", shared_channels=1, fc_num=1, weight_softmax=False, reduction="mean"):
+    def __init__(self, in_fdim, local_input_feature="dp", shared_channels=1, fc_num=1, weight_softmax=False, reduction="mean", activation_fn="relu"):
         super().__init__()
-        if fc_num != 1:
-            raise NotImplementedError("adaptive_weight.fc_num {}: only fc_num 1 is implemented (the fold of the FC layer holds for one layer)".format(fc_num))
+        if fc_num < 1:
+            raise ValueError("adaptive_weight.fc_num {}: at least 1".format(fc_num))
         S = _aw_options(local_input_feature, shared_channels, weight_softmax, reduction, in_fdim)
         d_in, M = _aw_d_in(local_input_feature, in_fdim), in_fdim // S
+        if fc_num != 1:
+            _aw_mlp_limits(fc_num, M)
         self.local_input_feature, self.shared_channels, self.fc_num = local_input_feature, shared_channels, fc_num
-        self.weight_softmax, self.reduction = weight_softmax, reduction
+        self.weight_softmax, self.reduction, self.activation_fn = weight_softmax, reduction, activation_fn
         self.weights = torch.nn.Parameter(torch.empty(d_in, M))
         _fan_in_init_(self.weights)
         self.biases = torch.nn.Parameter(torch.zeros(M))
+        for l in range(1, fc_num):
+            w = torch.nn.Parameter(torch.empty(M, M))
+            _fan_in_init_(w)
+            setattr(self, "weights_{}".format(l), w)
+            setattr(self, "biases_{}".format(l), torch.nn.Parameter(torch.zeros(M)))
+
+    def tf_scopes(self):
+        """parameter name -> the TF variable scope of its layer (:419-430): fc_0 .. fc_{fc_num-2} for the layers with an activation, fc_{fc_num} for the
+        last one — the number fc_num - 1 is skipped, which someone loading a reference checkpoint has to know"""
+        scope = lambda l: "fc_{}".format(l if l < self.fc_num - 1 else self.fc_num)
+        names = {"weights": scope(0), "biases": scope(0)}
+        for l in range(1, self.fc_num):
+            names["weights_{}".format(l)] = names["biases_{}".format(l)] = scope(l)
+        return names
 
     def forward(self, query_points, support_points, neighbors_indices, features, radius):
+        hidden = [(getattr(self, "weights_{}".format(l)), getattr(self, "biases_{}".format(l))) for l in range(1, self.fc_num)]
         return adaptive_weight(query_points, support_points, neighbors_indices, features, radius, self.weights, self.biases, self.reduction,
-                               local_input_feature=self.local_input_feature, shared_channels=self.shared_channels, weight_softmax=self.weight_softmax)
+                               local_input_feature=self.local_input_feature, shared_channels=self.shared_channels, weight_softmax=self.weight_softmax,
+                               fc_hidden=hidden, activation_fn=self.activation_fn)
 
 
 POSPOOL_EMBEDDINGS = {"one": 0, "xyz": 1, "distance": 2, "exp_-d": 3, "direction_exp_-d": 4, "direction_d": 5, "sin_cos": 6,

@@ -468,7 +468,38 @@ int cbl_adaptive_weight_general_backward_csr(int n, int n0, int K, int C, int M,
                                              float* grad_features_value, float* grad_center, float* grad_neighbor, float* grad_w_pos, float* grad_bias,
                                              void* workspace, size_t workspace_bytes, void* stream);
 
-/* a14  PosPool  tensorflow/models/local_aggregation_operators.py:15-250 (shipped: config/s3dis/pospool.yaml:20-23 'sin_cos' + 'mean')
+/* a14  AdaptiveWeight with fc_num 2 and 3  tensorflow/models/local_aggregation_operators.py:356, 419-430: `layers` = fc_num - 1 (1 or 2) further FC layers of
+ *   width M behind the folded first one, per pair (i,k):
+ *       y0 = the y[i,k,:] of cbl_adaptive_weight_general_forward (fc_0: w_pos, center_term, neighbor_term, bias)        h = act(y0)
+ *       h  = act(h @ hidden_w[l-1] + hidden_b[l-1])   for l = 1 .. layers-1        y = h @ hidden_w[layers-1] + hidden_b[layers-1]   (no activation)
+ *   and from y on weight_softmax, the multiply by f_j in groups of S and the reduction exactly as cbl_adaptive_weight_general_*.
+ *   hidden_w (layers,M,M) row-major and packed, in TF's (in, out) order; hidden_b (layers,M).  activation (basic_operators.py:285-289): 1 relu,
+ *   2 leaky_relu (alpha 0.2), any other value the identity.  Shadow pairs go through the layers like any other pair.
+ *   The layers run on v_mfma_f32_16x16x4_f32 (an fp32 fmaf chain) over tiles of whole queries held in LDS; nothing of shape (n,K,M) exists in memory.
+ *   Limits on top of the general entries': layers in {1, 2}, 16 <= M <= 144, K <= 48, or K <= 128 where M <= 64 (CBL_ERR_UNSUPPORTED otherwise, and
+ *   cbl_adaptive_weight_mlp_workspace_bytes returns 0).  Bad arguments return CBL_ERR_BAD_ARG before any launch.
+ *   No float atomics, every output written in a fixed summation order; no allocation or synchronisation inside a call.
+ *   workspace: cbl_adaptive_weight_mlp_workspace_bytes (one size for both calls; the forward call does not touch it). */
+size_t cbl_adaptive_weight_mlp_workspace_bytes(int n, int n0, int K, int C, int M, int layers);
+int cbl_adaptive_weight_mlp_forward(int n, int n0, int K, int C, int M, const float* query_points, const float* support_points,
+                                    const int* neighbors_indices, const float* features, const float* center_term, const float* neighbor_term,
+                                    const float* w_pos, const float* bias, int layers, const float* hidden_w, const float* hidden_b, int activation,
+                                    float radius, int softmax, int reduction, const int* padding_num, float* out, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+/* gradients (any may be NULL), all WRITTEN: those of cbl_adaptive_weight_general_backward_csr with dy carried back through the layers
+ * (dh = dz @ W^T, dz = dh * act'(h)) to dz0 at the first layer's output — grad_neighbor (n0,M) = sum over the pairs -> j of dz0, grad_center (n,M) per QUERY =
+ * sum_k dz0, grad_w_pos (3,M) = sum dp^T dz0, grad_bias (M) = sum dz0 — and grad_hidden_w (layers,M,M) = sum h^T dz, grad_hidden_b (layers,M) = sum dz.
+ * Sums over all pairs are per-workgroup partials added in a fixed order in fp64.  Under a softmax only the LAST layer's bias gradient is 0 by the shift
+ * invariance (written as exact zeros); grad_center and grad_bias are computed, the activation sits between them and the softmax. */
+int cbl_adaptive_weight_mlp_backward_csr(int n, int n0, int K, int C, int M, const float* query_points, const float* support_points,
+                                         const int* neighbors_indices, const float* features, const float* center_term, const float* neighbor_term,
+                                         const float* w_pos, const float* bias, int layers, const float* hidden_w, const float* hidden_b, int activation,
+                                         float radius, int softmax, int reduction, const int* padding_num, const float* out, const float* grad_out,
+                                         const int* order_dst, const int* inv_start, const int* inv_src, float* grad_features_value, float* grad_center,
+                                         float* grad_neighbor, float* grad_w_pos, float* grad_bias, float* grad_hidden_w, float* grad_hidden_b,
+                                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* a14  PosPool tensorflow/models/local_aggregation_operators.py:15-250 (shipped: config/s3dis/pospool.yaml:20-23 'sin_cos' + 'mean')
  *   out[p,c] = reduce_k geo[p,k,c/(C/mid)] * features[nbr(p,k),c]   (before pool_bn / activation / output_conv, :251-270)
  *   position_embedding: 0 'one' | 1 'xyz' | 2 'distance' | 3 'exp_-d' | 4 'direction_exp_-d' | 5 'direction_d' | 6 'sin_cos' |
  *                       7 'two_order' | 8 'three_order'   ('direction' alone cannot run in the reference: mid_fdim 1 vs a 3-vector, :93-96)
