@@ -158,7 +158,9 @@ __global__ __launch_bounds__(KB_NB) void kpconv_bwd_csr_kernel(unsigned n0, int 
             }
             if (GKW) {
                 const float4 fj = *reinterpret_cast<const float4*>(f + (size_t)j * C + cb);
-                const float fv[4] = {fj.x, fj.y, fj.z, fj.w};
+                // a target nobody lists has S = 0 and takes no part, whatever its row holds: a non-finite feature there must not leak as inf * 0
+                const bool listed = s1 > s0;
+                const float fv[4] = {listed ? fj.x : 0.f, listed ? fj.y : 0.f, listed ? fj.z : 0.f, listed ? fj.w : 0.f};
 #pragma unroll
                 for (int t = 0; t < 4; t++)
 #pragma unroll

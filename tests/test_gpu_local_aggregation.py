@@ -284,7 +284,7 @@ def test_kpconv_shadow_neighbours_do_not_read_row_zero():
     table holds: the kernels load from a clamped row 0 unconditionally, and a non-finite value there must not leak as 0 * inf"""
     from contrastboundary_amd import local_aggregation as L
     q, s, idx, f, rng = make(600, 300, 12, 32, seed=3)
-    idx = idx.copy(); idx[::3, -4:] = 300                              # shadow neighbours on every third point
+    idx = idx.copy(); idx[::3, -4:] = 600                              # shadow neighbours (the shadow index is n0 = 600) on every third point
     kpts = (rng.normal(size=(15, 3)) * 0.06).astype(np.float32); kpts[0] = 0
     kw = rng.normal(size=(15, 32)).astype(np.float32)
     ref = LA.kpconv(q, s, idx, f, kpts, kw, 0.09, "constant", "sum")
