@@ -352,8 +352,10 @@ CBL_EXPORT int cbl_pospool_forward(int n, int n0, int K, int C, const float* que
     const int rc = pospool_check(n, n0, K, C, radius, position_embedding, reduction);
     if (rc) return rc;
     if (n == 0) return CBL_OK;
-    if (!query_points || !support_points || !neighbors_indices || !features || !out || (reduction == RED_MEAN && !padding_num)) return CBL_ERR_BAD_ARG;
-    const bool vec = reduction != RED_MAX && (C % 4 == 0) && ((((uintptr_t)features | (uintptr_t)out) & 15) == 0);
+    // an empty support set (n0 == 0) has no buffers to point at: torch hands out a null pointer for an empty tensor, and neither kernel touches them then
+    if (!query_points || !neighbors_indices || !out || (n0 > 0 && (!support_points || !features)) || (reduction == RED_MEAN && !padding_num)) return CBL_ERR_BAD_ARG;
+    // n0 == 0: every entry is the shadow neighbour, and pospool_fwd_v4 loads row 0 of features / support_points before it skips one — pospool_kernel predicates them
+    const bool vec = reduction != RED_MAX && (C % 4 == 0) && ((((uintptr_t)features | (uintptr_t)out) & 15) == 0) && n0 > 0;
     if (vec) {
         const int C4 = C / 4, chunks = (C4 + 255) / 256, Lmax = (C4 + chunks - 1) / chunks;
         for (int c4_0 = 0; c4_0 < C4; c4_0 += Lmax) {
@@ -378,7 +380,7 @@ CBL_EXPORT int cbl_pospool_backward(int n, int n0, int K, int C, const float* qu
 {
     const int rc = pospool_check(n, n0, K, C, radius, position_embedding, reduction);
     if (rc) return rc;
-    if (n == 0) return CBL_OK;
+    if (n == 0 || n0 == 0) return CBL_OK;                                          // no support row, no gradient row
     if (!query_points || !support_points || !neighbors_indices || !features || !grad_out || !grad_features || (reduction == RED_MEAN && !padding_num))
         return CBL_ERR_BAD_ARG;
     hipLaunchKernelGGL(pospool_kernel<true>, dim3(pp_grid(n)), dim3(256), 0, cbl_stream(stream), n, n0, K, C, query_points, support_points,
