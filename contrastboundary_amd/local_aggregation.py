@@ -2,7 +2,7 @@
     kpconv (PseudoGrid)   /root/reference/tensorflow/models/local_aggregation_operators.py:620-746
     adaptive_weight       ...:316-500 (fc_num 1, 2, 3; the shipped options, config/s3dis/adapt.yaml:19-26, on kernels of their own)
     pospool               ...:15-250
-    pointwise_mlp         ...:503-617 (fc_num 1; its batch norm and activation sit INSIDE the per-pair MLP, before the reduction: part of the kernels)
+    pointwise_mlp         ...:503-617 (fc_num 1, 2, 3; its batch norm and activation sit INSIDE the per-pair MLP, before the reduction: part of the kernels)
     ind_max_pool / ind_closest_pool   /root/reference/tensorflow/models/basic_operators.py:155-192
 Arguments keep the reference's names and order (query_points, support_points, neighbors_indices, features, ...); the
 trainable variables the TF code creates inside its variable scope (kernel weights, FC weight/bias) are explicit tensors.
@@ -571,16 +571,136 @@ class _PointWiseMLP(Function):
         return (None, None, None, gcen, gn, gwp, gg, gb) + (None,) * 8
 
 
+class _PointWiseMLPLayers(Function):
+    """the two entries of csrc/pointwise_mlp_layers.hip around the folded per-point terms of fc_0 (cbl_amd.h, a14 PointWiseMLP with fc_num 2 and 3).
+    hidden_w: the weights behind the first layer, flattened and packed in order; gamma / beta / moving_mean / moving_variance: packed over the layers
+    (layers * H + C_out), the moving statistics as ONE buffer the kernels update in place (the caller copies it back)"""
+
+    @staticmethod
+    def forward(ctx, query_points, support_points, neighbors_indices, center_term, neighbor_term, w_pos, hidden_w, gamma, beta, moving_mean, moving_variance,
+                radius, bn_mode, act, red, momentum, eps, C_out, layers):
+        n, K = neighbors_indices.shape
+        n0, H = neighbor_term.shape
+        L = _lib.lib()
+        dev = neighbor_term.device
+        st = _lib.stream_of(neighbor_term)
+        pad = torch.empty(1, dtype=torch.int32, device=dev)
+        if red == 1:
+            _lib.check(L.cbl_index_max(ctypes.c_longlong(n * K), _lib.ptr(neighbors_indices), _lib.ptr(pad), st), "cbl_index_max")
+        out = torch.empty((n, C_out), dtype=torch.float32, device=dev)
+        WT = layers * H + C_out
+        save_mean = torch.empty(WT, dtype=torch.float32, device=dev) if bn_mode else None
+        save_invstd = torch.empty(WT, dtype=torch.float32, device=dev) if bn_mode else None
+        ws = torch.empty(max(L.cbl_pointwise_mlp_layers_workspace_bytes(_i(n), _i(n0), _i(K), _i(H), _i(C_out), _i(layers)), 1), dtype=torch.uint8, device=dev)
+        _lib.check(L.cbl_pointwise_mlp_layers_forward(_i(n), _i(n0), _i(K), _i(H), _i(C_out), _lib.ptr(query_points), _lib.ptr(support_points),
+                                                      _lib.ptr(neighbors_indices), _lib.ptr(center_term), _lib.ptr(neighbor_term), _lib.ptr(w_pos), _f(radius),
+                                                      _i(layers), _lib.ptr(hidden_w), _i(bn_mode), _lib.ptr(gamma), _lib.ptr(beta), _f(eps), _f(momentum),
+                                                      _lib.ptr(moving_mean), _lib.ptr(moving_variance), _i(act), _i(red), _lib.ptr(pad), _lib.ptr(save_mean),
+                                                      _lib.ptr(save_invstd), _lib.ptr(out), _lib.ptr(ws), ctypes.c_size_t(ws.numel()), st),
+                   "cbl_pointwise_mlp_layers_forward")
+        ctx.save_for_backward(query_points, support_points, neighbors_indices, center_term, neighbor_term, w_pos, hidden_w, gamma, beta, save_mean,
+                              save_invstd, pad, out)
+        ctx.cfg = (radius, bn_mode, act, red, C_out, layers)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        q, s, idx, cen, nbr, wp, hw, gamma, beta, save_mean, save_invstd, pad, out = ctx.saved_tensors
+        radius, bn_mode, act, red, C_out, layers = ctx.cfg
+        n, K = idx.shape
+        n0, H = nbr.shape
+        grad_out = grad_out.contiguous()
+        L = _lib.lib()
+        dev = nbr.device
+        st = _lib.stream_of(nbr)
+        from . import pointops
+        need = ctx.needs_input_grad
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        WT = layers * H + C_out
+        gc = new(n, H) if cen is not None and need[3] else None
+        gn = new(n0, H) if need[4] else None
+        gwp = new(3, H) if wp is not None and need[5] else None
+        ghw = new(hw.numel()) if need[6] else None
+        gg = new(WT) if gamma is not None and need[7] else None
+        gb = new(WT) if beta is not None and need[8] else None
+        order = inv_start = inv_src = None
+        if gn is not None:
+            tr = pointops.neighbor_transpose(idx, n0, build=True)
+            if tr is None:
+                raise NotImplementedError("pointwise_mlp: no transposed neighbour table for more than 2^20 support points, and there is no scatter form")
+            order, inv_start, inv_src = tr
+        ws = torch.empty(max(L.cbl_pointwise_mlp_layers_workspace_bytes(_i(n), _i(n0), _i(K), _i(H), _i(C_out), _i(layers)), 1), dtype=torch.uint8, device=dev)
+        _lib.check(L.cbl_pointwise_mlp_layers_backward_csr(_i(n), _i(n0), _i(K), _i(H), _i(C_out), _lib.ptr(q), _lib.ptr(s), _lib.ptr(idx), _lib.ptr(cen),
+                                                           _lib.ptr(nbr), _lib.ptr(wp), _f(radius), _i(layers), _lib.ptr(hw), _i(bn_mode), _lib.ptr(gamma),
+                                                           _lib.ptr(beta), _lib.ptr(save_mean), _lib.ptr(save_invstd), _i(act), _i(red), _lib.ptr(pad),
+                                                           _lib.ptr(out), _lib.ptr(grad_out), _lib.ptr(order), _lib.ptr(inv_start), _lib.ptr(inv_src),
+                                                           _lib.ptr(gc), _lib.ptr(gn), _lib.ptr(gwp), _lib.ptr(ghw), _lib.ptr(gg), _lib.ptr(gb), _lib.ptr(ws),
+                                                           ctypes.c_size_t(ws.numel()), st), "cbl_pointwise_mlp_layers_backward_csr")
+        gcen = None
+        if gc is not None:
+            # per-query rows onto the centre rows they came from, as _PointWiseMLP does
+            tr0 = pointops.neighbor_transpose(idx[:, :1].contiguous(), n0, build=True)
+            if tr0 is None:
+                raise NotImplementedError("pointwise_mlp: no transposed neighbour table for more than 2^20 support points, and there is no scatter form")
+            gcen = new(n0, H)
+            _lib.check(L.cbl_grouping_backward_csr_rows(_i(n0), _i(H), _i(H), _i(0), _lib.ptr(gc), _lib.ptr(tr0[0]), _lib.ptr(tr0[1]), _lib.ptr(tr0[2]),
+                                                        _lib.ptr(gcen), st), "cbl_grouping_backward_csr_rows")
+        return (None, None, None, gcen, gn, gwp, ghw, gg, gb) + (None,) * 10
+
+
+_PW_LAYERS_H = (16, 144)        # the hidden widths csrc/pointwise_mlp_layers.hip takes (one matrix tile .. half the ConvNet's widest bottleneck)
+
+
+def _pw_layers_limits(fc_num, H, K=None):
+    """refuses the depths, widths and neighbour counts the per-pair layer kernels do not cover, naming fc_num"""
+    if fc_num < 1 or fc_num > 3:
+        raise NotImplementedError("pointwisemlp.fc_num {}: fc_num 1, 2 and 3 are implemented".format(fc_num))
+    if not _PW_LAYERS_H[0] <= H <= _PW_LAYERS_H[1]:
+        raise NotImplementedError("pointwisemlp.fc_num {}: only fc_num 1 is implemented for hidden layers of width {} (the per-pair layer kernels take {} "
+                                  "to {})".format(fc_num, H, *_PW_LAYERS_H))
+    if K is not None and (K > 128 or (K > 48 and H > 64)):
+        raise NotImplementedError("pointwisemlp.fc_num {}: {} neighbours with hidden layers of width {} (at most 48, or 128 up to width 64)".format(fc_num, K, H))
+
+
 def pointwise_mlp(query_points, support_points, neighbors_indices, features, radius, weights, gamma=None, beta=None, moving_mean=None,
                   moving_variance=None, *, local_input_feature="dp_fj", reduction="max", activation_fn="relu", is_training=True, bn_momentum=0.98,
-                  bn_eps=1e-3, fc_num=1):
-    """PointWiseMLP (n, out_fdim)  (tensorflow/models/local_aggregation_operators.py:503-617; options as config.pointwisemlp.*) with fc_num 1.
-    weights: the TF variable fc_1/weights (D_in, C_out), rows in the concatenation order of :573-584; gamma / beta: its batch norm (gamma None: bn=False);
-    moving_mean / moving_variance: updated in place when training (TF convention), used when not.
-    One FC layer is linear in the concatenated blocks: y = dp @ W_p + (f @ (W_fi - W_df))[idx[:, 0]] + (f @ (W_df + W_fj))[idx] — the two per-point products
-    are dense layers here (autograd carries the fold and the weight gradient), the per-pair part is csrc/pointwise_mlp.hip."""
-    if fc_num != 1:
-        raise NotImplementedError("pointwisemlp.fc_num {}: only fc_num 1 is implemented (the fold of the FC layer holds for one layer)".format(fc_num))
+                  bn_eps=1e-3, fc_num=None, fc_hidden=()):
+    """PointWiseMLP (n, out_fdim)  (tensorflow/models/local_aggregation_operators.py:503-617; options as config.pointwisemlp.*) with fc_num 1 + len(fc_hidden)
+    (1, 2 or 3).  weights: the TF variable of the FIRST layer (D_in, width), rows in the concatenation order of :573-584 — fc_1/weights (D_in, C_out) for
+    fc_num 1, fc_0/weights (D_in, H) with H = max(in_fdim // 2, 9) otherwise; gamma / beta: its batch norm (gamma None: bn=False); moving_mean /
+    moving_variance: updated in place when training (TF convention), used when not.
+    The first layer is linear in the concatenated blocks: y = dp @ W_p + (f @ (W_fi - W_df))[idx[:, 0]] + (f @ (W_df + W_fj))[idx] — the two per-point products
+    are dense layers here (autograd carries the fold and the weight gradient), the per-pair part is csrc/pointwise_mlp.hip.
+    fc_hidden: the layers behind the first, in order, each (weights (in, out), gamma, beta, moving_mean, moving_variance) with the last four None exactly
+    when the first layer's gamma is None (:589-600: no layer has a bias, every layer its own batch norm over all n*K pair rows and the activation; the last
+    one is (H, C_out)).  The per-pair part is then csrc/pointwise_mlp_layers.hip (16 <= H <= 144; K <= 48, or <= 128 up to H = 64).  fc_num None:
+    1 + len(fc_hidden); a given fc_num that disagrees with the layers passed is refused.  With fc_hidden empty the call is fc_num 1's."""
+    fc_hidden = tuple(fc_hidden)
+    if fc_num is None:
+        fc_num = 1 + len(fc_hidden)
+    if fc_num != 1 + len(fc_hidden):
+        raise NotImplementedError("pointwisemlp.fc_num {}: {} layer(s) were passed (weights and fc_hidden); fc_num 2 and 3 take the layers behind the first "
+                                  "in fc_hidden".format(fc_num, 1 + len(fc_hidden)))
+    if fc_hidden:
+        _pw_layers_limits(fc_num, weights.shape[1], neighbors_indices.shape[1])
+        for l, layer in enumerate(fc_hidden, 1):
+            if len(layer) != 5:
+                raise ValueError("fc_hidden[{}]: (weights, gamma, beta, moving_mean, moving_variance) expected".format(l - 1))
+            if any((t is None) != (gamma is None) for t in layer[1:3]) or (gamma is None and any(t is not None for t in layer[3:])):
+                raise ValueError("fc_hidden[{}]: batch-norm variables present on one layer and absent on another (one bn setting holds for every "
+                                 "layer)".format(l - 1))
+            H = weights.shape[1]
+            if layer[0].dim() != 2 or layer[0].shape[0] != H or (l < len(fc_hidden) and layer[0].shape[1] != H):
+                raise ValueError("fc_hidden[{}]: weights of shape {}, behind a layer of width {} it has ({}, {})".format(
+                    l - 1, tuple(layer[0].shape), H, H, H if l < len(fc_hidden) else "out_fdim"))
+            width = layer[0].shape[1]
+            for t, name in zip(layer[1:], ("gamma", "beta", "moving_mean", "moving_variance")):
+                if t is not None and tuple(t.shape) != (width,):
+                    raise ValueError("fc_hidden[{}]: {} of shape {}, a layer of width {} has ({},)".format(l - 1, name, tuple(t.shape), width, width))
+            _chk(layer[0], torch.float32, "fc_hidden[{}] weights".format(l - 1))
+            for t, name in zip(layer[1:], ("gamma", "beta", "moving_mean", "moving_variance")):
+                if t is not None:
+                    _chk(t, torch.float32, "fc_hidden[{}] {}".format(l - 1, name))
     _chk(query_points, torch.float32, "query_points"); _chk(support_points, torch.float32, "support_points")
     _chk(neighbors_indices, torch.int32, "neighbors_indices"); _chk(features, torch.float32, "features")
     _chk(weights, torch.float32, "weights")
@@ -591,16 +711,16 @@ def pointwise_mlp(query_points, support_points, neighbors_indices, features, rad
         raise NotImplementedError("local_input_feature {} not supported in Point-wise MLP".format(local_input_feature))
     if reduction not in _PW_REDUCTIONS:
         raise NotImplementedError("Reduction {} not supported in Point-wise MLP.".format(reduction))
-    C, C_out, K = features.shape[1], weights.shape[1], neighbors_indices.shape[1]
+    C, C_out, K = features.shape[1], (fc_hidden[-1][0] if fc_hidden else weights).shape[1], neighbors_indices.shape[1]
     has_dp, has_fi, has_fj = local_input_feature.startswith("dp"), "fi_df" in local_input_feature, local_input_feature.endswith("fj")
     if weights.shape[0] != 3 * has_dp + 2 * C * has_fi + C * has_fj:
         raise ValueError("weights: {} rows, local_input_feature {} of {} features has {}".format(weights.shape[0], local_input_feature, C,
                                                                                               3 * has_dp + 2 * C * has_fi + C * has_fj))
     if C_out % 4 != 0 or C_out > 1024:
-        raise NotImplementedError("pointwise_mlp: out_fdim {} (a multiple of 4 up to 1024)".format(C_out))
+        raise NotImplementedError("pointwise_mlp: out_fdim {} (a multiple of 4 up to 1024, for fc_num 1, 2 and 3)".format(C_out))
     if K > 128:
         raise NotImplementedError("pointwise_mlp: {} neighbours (at most 128)".format(K))
-    if gamma is not None and not is_training and (moving_mean is None or moving_variance is None):
+    if gamma is not None and not is_training and any(t is None for t in (moving_mean, moving_variance) + tuple(t for h in fc_hidden for t in h[3:])):
         raise ValueError("pointwise_mlp: is_training=False needs moving_mean and moving_variance")
     from . import dense
     o = 3 if has_dp else 0
@@ -615,39 +735,81 @@ def pointwise_mlp(query_points, support_points, neighbors_indices, features, rad
         w_n = weights[o:o + C]
     neighbor_term = dense.linear(features, w_n.t())
     bn_mode = 0 if gamma is None else (1 if is_training else 2)
+    if fc_hidden:
+        layers, H = len(fc_hidden), weights.shape[1]
+        hidden_w = torch.cat([h[0].reshape(-1) for h in fc_hidden])
+        pack = lambda first, k: None if first is None else torch.cat([first] + [h[k] for h in fc_hidden])
+        moving = [(moving_mean, moving_variance)] + [(h[3], h[4]) for h in fc_hidden]
+        mm = mv = None
+        if bn_mode and all(m is not None and v is not None for m, v in moving):
+            with torch.no_grad():
+                mm, mv = torch.cat([m for m, _ in moving]), torch.cat([v for _, v in moving])
+        out = _PointWiseMLPLayers.apply(query_points, support_points, neighbors_indices, center_term, neighbor_term.contiguous(), w_pos, hidden_w,
+                                        pack(gamma, 1), pack(beta, 2), mm, mv, float(radius), bn_mode, _PW_ACTIVATIONS.get(activation_fn, 0),
+                                        _PW_REDUCTIONS[reduction], float(bn_momentum), float(bn_eps), C_out, layers)
+        if bn_mode == 1 and mm is not None:                          # every layer's moving statistics, updated by the kernels in the packed buffer
+            with torch.no_grad():
+                o = 0
+                for m, v in moving:
+                    m.copy_(mm[o:o + m.numel()]); v.copy_(mv[o:o + v.numel()])
+                    o += m.numel()
+        return out
     return _PointWiseMLP.apply(query_points, support_points, neighbors_indices, center_term, neighbor_term.contiguous(), w_pos, gamma, beta, moving_mean,
                                moving_variance, float(radius), bn_mode, _PW_ACTIVATIONS.get(activation_fn, 0), _PW_REDUCTIONS[reduction],
                                float(bn_momentum), float(bn_eps))
 
 
 class PointWiseMLP(torch.nn.Module):
-    """the operator with its variables: fc_1/weights (xavier), fc_1/bn gamma, beta and the moving statistics (TF names)"""
+    """the operator with its variables (TF names): `weights` (xavier), `gamma`, `beta` and the moving statistics of the first layer — fc_1 (D_in, out_fdim)
+    for fc_num 1, fc_0 (D_in, H) with H = max(in_fdim // 2, 9) for fc_num 2 and 3 — and `weights_l`, `gamma_l`, `beta_l`, `moving_mean_l`,
+    `moving_variance_l` of the layers l = 1 .. fc_num - 1 behind it ((H, H), the last one (H, out_fdim); :589-600)"""
 
     def __init__(self, in_fdim, out_fdim, local_input_feature="dp_fj", fc_num=1, reduction="max", activation_fn="relu", bn=True, bn_momentum=0.98,
                  bn_eps=1e-3):
         super().__init__()
+        H = max(in_fdim // 2, 9)
         if fc_num != 1:
-            raise NotImplementedError("pointwisemlp.fc_num {}: only fc_num 1 is implemented (the fold of the FC layer holds for one layer)".format(fc_num))
+            _pw_layers_limits(fc_num, H)
         if local_input_feature not in POINTWISE_MLP_INPUTS:
             raise NotImplementedError("local_input_feature {} not supported in Point-wise MLP".format(local_input_feature))
         d_in = 3 * local_input_feature.startswith("dp") + 2 * in_fdim * ("fi_df" in local_input_feature) + in_fdim * local_input_feature.endswith("fj")
         self.local_input_feature, self.fc_num, self.reduction, self.activation_fn = local_input_feature, fc_num, reduction, activation_fn
         self.bn_momentum, self.bn_eps = bn_momentum, bn_eps
-        self.weights = torch.nn.Parameter(torch.empty(d_in, out_fdim))
-        torch.nn.init.xavier_uniform_(self.weights)
-        if bn:
-            self.gamma = torch.nn.Parameter(torch.ones(out_fdim))
-            self.beta = torch.nn.Parameter(torch.zeros(out_fdim))
-            self.register_buffer("moving_mean", torch.zeros(out_fdim))
-            self.register_buffer("moving_variance", torch.ones(out_fdim))
-        else:
-            self.gamma = self.beta = self.moving_mean = self.moving_variance = None
+        ins = [d_in] + [H] * (fc_num - 1)
+        outs = [H] * (fc_num - 1) + [out_fdim]
+        for l, (i, o) in enumerate(zip(ins, outs)):
+            tag = "" if l == 0 else "_{}".format(l)
+            w = torch.nn.Parameter(torch.empty(i, o))
+            torch.nn.init.xavier_uniform_(w)
+            setattr(self, "weights" + tag, w)
+            if bn:
+                setattr(self, "gamma" + tag, torch.nn.Parameter(torch.ones(o)))
+                setattr(self, "beta" + tag, torch.nn.Parameter(torch.zeros(o)))
+                self.register_buffer("moving_mean" + tag, torch.zeros(o))
+                self.register_buffer("moving_variance" + tag, torch.ones(o))
+            else:
+                for name in ("gamma", "beta", "moving_mean", "moving_variance"):
+                    setattr(self, name + tag, None)
+
+    def tf_scopes(self):
+        """variable name -> the TF variable scope of its layer (:590-600): fc_0 .. fc_{fc_num-2} for the hidden layers, fc_{fc_num} for the last one — the
+        number fc_num - 1 is skipped (fc_num 1: fc_1 alone), which someone loading a reference checkpoint has to know"""
+        scope = lambda l: "fc_{}".format(l if l < self.fc_num - 1 else self.fc_num)
+        names = {}
+        for l in range(self.fc_num):
+            tag = "" if l == 0 else "_{}".format(l)
+            for name in ("weights", "gamma", "beta", "moving_mean", "moving_variance"):
+                if getattr(self, name + tag) is not None:
+                    names[name + tag] = scope(l)
+        return names
 
     def forward(self, query_points, support_points, neighbors_indices, features, radius):
+        hidden = [tuple(getattr(self, name + "_{}".format(l)) for name in ("weights", "gamma", "beta", "moving_mean", "moving_variance"))
+                  for l in range(1, self.fc_num)]
         return pointwise_mlp(query_points, support_points, neighbors_indices, features, radius, self.weights, self.gamma, self.beta, self.moving_mean,
                              self.moving_variance, local_input_feature=self.local_input_feature, reduction=self.reduction,
                              activation_fn=self.activation_fn, is_training=self.training, bn_momentum=self.bn_momentum, bn_eps=self.bn_eps,
-                             fc_num=self.fc_num)
+                             fc_num=self.fc_num, fc_hidden=hidden)
 
 
 def _ind_max_pool_forward(x, inds):

@@ -554,7 +554,40 @@ int cbl_pointwise_mlp_backward_csr(int n, int n0, int K, int C_out, const float*
                                    float* grad_center, float* grad_neighbor, float* grad_w_pos, float* grad_gamma, float* grad_beta,
                                    void* workspace, size_t workspace_bytes, void* stream);
 
-/* a4  PointTransformerLayer  pytorch/model/blocks.py:31-44, the C-wide part without its (n,K,C) tensors (C = 32 or 64, G = C/8):
+/* a14  PointWiseMLP with fc_num 2 and 3  (:589-600: hidden layers of width H = max(in_fdim / 2, 9), none with a bias, EVERY layer with its own batch norm over
+ *   all n*K pair rows, shadow rows included, and the activation).  layers = fc_num - 1 in {1, 2}; for the pair (i,k) with neighbour j = idx[i,k]
+ *       y_0 = ((s_j - q_i)/radius) @ w_pos (3,H)  +  center_term[idx[i,0]]  +  neighbor_term[j]          the fold of the first layer, terms (n0,H) by the caller
+ *       h_l = act( gamma_l * (y_l - mean_l) * invstd_l + beta_l )     l = 0 .. layers          y_{l+1} = h_l @ W_{l+1}
+ *       out[i,:] = reduce_k  mask[i,k] * h_layers                      (n,C_out)
+ *   hidden_w: the weights behind the first layer, packed in TF's (in,out) order: [W_1 (H,H) when layers == 2] then W_layers (H,C_out).
+ *   gamma / beta / moving_mean / moving_var / save_mean / save_invstd (and grad_gamma / grad_beta): one packed vector each of layers*H + C_out floats,
+ *   layer l < layers at l*H (H wide), the last layer at layers*H (C_out wide).  bn_mode, eps, momentum, activation, reduction, padding_num as in
+ *   cbl_pointwise_mlp_forward; one bn_mode for every layer; every layer's moving statistics are updated under bn_mode 1.
+ *   Nothing of shape (n,K,.) is stored: with batch statistics the forward call is layers + 2 sweeps over the pairs (the statistics of layer l are final
+ *   before layer l + 1 is formed), each recomputing the pairs from their rows on f32 MFMA tiles in LDS; bn_mode 0 / 2: one sweep.
+ *   layers in {1,2}; 16 <= H <= 144; C_out % 4 == 0, C_out <= 1024; K <= 48, or K <= 128 while H <= 64 (CBL_ERR_UNSUPPORTED otherwise, and
+ *   cbl_pointwise_mlp_layers_workspace_bytes returns 0).  Bad arguments return CBL_ERR_BAD_ARG before any launch; n == 0 is a no-op.  No float atomics: every
+ *   output is stored once in a fixed summation order; no allocation or synchronisation inside a call.  workspace: one size for both calls. */
+size_t cbl_pointwise_mlp_layers_workspace_bytes(int n, int n0, int K, int H, int C_out, int layers);
+int cbl_pointwise_mlp_layers_forward(int n, int n0, int K, int H, int C_out, const float* query_points, const float* support_points,
+                                     const int* neighbors_indices, const float* center_term, const float* neighbor_term, const float* w_pos, float radius,
+                                     int layers, const float* hidden_w, int bn_mode, const float* gamma, const float* beta, float eps, float momentum,
+                                     float* moving_mean, float* moving_var, int activation, int reduction, const int* padding_num, float* save_mean,
+                                     float* save_invstd, float* out, void* workspace, size_t workspace_bytes, void* stream);
+/* gradients (any may be NULL), all WRITTEN: grad_center (n,H) per QUERY = sum_k dy_0[i,k,:] (the caller scatters it through idx[:,0]), grad_neighbor (n0,H) as a
+ * gather over the transposed table of neighbors_indices (cbl_neighbor_transpose with n0 targets, pairs p = i*K + k; needed only for grad_neighbor),
+ * grad_w_pos (3,H), grad_hidden_w (packed as hidden_w), grad_gamma / grad_beta (packed as gamma).  Per layer under bn_mode 1:
+ * dy_l = gamma_l * invstd_l * (dz_l - sum dz_l / N - xhat_l * sum(dz_l * xhat_l) / N), N = n*K: the sums of layer l are final before dy_l is formed, so the
+ * query side is layers + 2 sweeps (one per layer's sums, one for dy_0), the target side one; bn_mode 0 / 2: one sweep each. */
+int cbl_pointwise_mlp_layers_backward_csr(int n, int n0, int K, int H, int C_out, const float* query_points, const float* support_points,
+                                          const int* neighbors_indices, const float* center_term, const float* neighbor_term, const float* w_pos,
+                                          float radius, int layers, const float* hidden_w, int bn_mode, const float* gamma, const float* beta,
+                                          const float* save_mean, const float* save_invstd, int activation, int reduction, const int* padding_num,
+                                          const float* out, const float* grad_out, const int* order_dst, const int* inv_start, const int* inv_src,
+                                          float* grad_center, float* grad_neighbor, float* grad_w_pos, float* grad_hidden_w, float* grad_gamma,
+                                          float* grad_beta, void* workspace, size_t workspace_bytes, void* stream);
+
+/* a4  PointTransformerLayer pytorch/model/blocks.py:31-44, the C-wide part without its (n,K,C) tensors (C = 32 or 64, G = C/8):
  *   p1 (n,K,3) = ReLU(BN(Linear(3,3)(p_j - p_i)))  [computed by the caller: narrow],  p_r = Linear(3,C)(p1) = p1 @ W3C^T + b3C  [never stored]
  * attn_w2:  w2 (n,K,G) = Linear(C,G)( ReLU( BN_C( x_k[idx] - x_q + p_r ) ) )       (:39 and the first half of linear_w, :25-27)
  *   training != 0: BatchNorm statistics over all n*K pairs (one extra pass), running stats / counter updated like nn.BatchNorm1d, batch mean /
