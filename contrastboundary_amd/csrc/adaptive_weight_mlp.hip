@@ -8,11 +8,12 @@
 // any other (zero rows, their point at the origin).  act: 1 relu, 2 leaky_relu (alpha 0.2), anything else the identity (basic_operators.py:285-289).
 //
 // MI355X mapping.  The product h @ W crosses the lanes, so the pairs of a few queries are a small dense matrix in LDS: a workgroup (four waves) takes a tile of
-// whole queries per trip, R = their pair rows padded to a multiple of 16, the M columns zero-padded to MP = a multiple of 16 inside the kernel.
+// whole queries per trip, R = their pair rows padded to a multiple of 16, the M columns zero-padded to MP = a multiple of 16 inside the kernel.  The row
+// convention, the y0 fold, the weight-gradient tiles, the target-side chunk walk and the host-side tile planning are pair_tile.h's, shared with
+// pointwise_mlp_layers.hip; the layer product keeps pair_tile.h's lane layout in a loop of its own (awm_layer).
 //   rows    : the y0 rows are made on the VALU (one thread per (row, column)) into LDS
-//   layers  : per 16-row tile a chain of v_mfma_f32_16x16x4_f32 (an exact fp32 fmaf chain); a wave owns its row tile across all MP / 16 column tiles
-//             (accumulators in registers), so the forward pass runs the layers in place.  The weights are the B operand, read from global memory
-//             (at most 2 x 81 KB, shared by every workgroup: L2 / L1 resident)
+//   layers  : a wave owns its 16-row tile across all MP / 16 column tiles (accumulators in registers), so the forward pass runs the layers in place.
+//             The weights are the B operand, read from global memory (at most 2 x 81 KB, shared by every workgroup: L2 / L1 resident)
 //   weights : a thread per (query, group) walks the K logits of its column in LDS: running max / sum, then y -> w in place
 //   reduce  : a thread per (query, float4 of channels) walks the K pairs: w from LDS, f_j from memory
 //   forward   F : rows, layers, weights, reduce -> out
@@ -22,26 +23,21 @@
 //                 grad_center = sum_k dz0, partial sums of grad_w_pos and grad_bias0.  lse, D, 1 / nn and the ties go to the workspace.
 //                 A finalize kernel adds the workgroups' partials in a fixed order in fp64.
 //             BT: by target, over the transposed table: chunks of R pairs of a trip's targets recompute the forward (and, when grad_neighbor is asked for, the
-//                 backward walk to dz0) reading lse / D / 1 / nn / ties; a thread per (target, float4) sums da w, a thread per (target, column) sums dz0.  A target
-//                 whose pairs span several chunks is continued by the same thread of the same workgroup (stored at its first chunk, added to afterwards).
+//                 backward walk to dz0) reading lse / D / 1 / nn / ties; a thread per (target, float4) sums da w, a thread per (target, column) sums dz0.
 // Under a softmax sum_k dy = 0 exactly: the LAST layer's bias gradient is written as zeros.  That shortcut does not hold for the first layer any more
 // (the activation sits between): grad_center and grad_bias0 are computed.
 // No float atomics; every output is stored by one thread in a fixed order.  LDS: one of three static sizes (24 / 56 / 96 KB of rows + 7 KB of row data), the
 // smallest that holds a useful tile — gfx950 has 160 KB per compute unit; rows are MP + 4 floats apart where the tile still fits (the 16 rows of an A operand
 // then fall into different banks), MP where not.
-#include "cbl_common.h"
+#include "pair_tile.h"
 
 namespace {
 
-using awm_f32x4 = __attribute__((ext_vector_type(4))) float;
-
 enum { AWM_SM_NONE = 0, AWM_SM_MASKED = 1, AWM_SM_UNMASK = 2 };
-enum { AWM_SUM = 0, AWM_MEAN = 1, AWM_MAX = 2 };
-constexpr int AWM_BLOCK = 256, AWM_WAVES = 4, AWM_RMAX = 256, AWM_NCT = 9;
 constexpr int AWM_MMIN = 16, AWM_MMAX = 144, AWM_KMAX = 128, AWM_KWIDE = 48, AWM_MNARROW = 64, AWM_CMAX = 1152;
 // grid caps (four workgroups of the smallest LDS size per compute unit: a trip is a chain of short phases behind barriers, other workgroups fill its waits);
-// BQ's also bounds the partials: at most AWM_BQ_PARTIAL floats of them, never fewer than AWM_BQ_BLOCKS_MIN workgroups; the most targets of a BT trip
-constexpr int AWM_F_BLOCKS = 1024, AWM_BQ_BLOCKS = 1024, AWM_BQ_BLOCKS_MIN = 256, AWM_BQ_PARTIAL = 1 << 24, AWM_BT_BLOCKS = 1024, AWM_TPT_MAX = 16;
+// BQ's also bounds the partials: at most PAIR_BQ_PARTIAL floats of them, never fewer than AWM_BQ_BLOCKS_MIN workgroups
+constexpr int AWM_F_BLOCKS = 1024, AWM_BQ_BLOCKS = 1024, AWM_BQ_BLOCKS_MIN = 256, AWM_BT_BLOCKS = 1024;
 constexpr int AWM_LDS0 = 6144, AWM_LDS1 = 14336, AWM_LDS2 = 24576;                                 // floats of row buffers
 constexpr float AWM_SHADOW_MAX = -65535.f;                                                         // :475
 
@@ -60,15 +56,11 @@ struct AwmBwd {
 struct AwmLds { float* buf; float* dp; int* rowI; int* rowJ; int* rowC; float* cnt; };
 
 #define AWM_LDS_DECL(L)                                                                                                              \
-    __shared__ float awm_buf[LDSF]; __shared__ float awm_dp[AWM_RMAX * 3]; __shared__ int awm_ri[AWM_RMAX]; __shared__ int awm_rj[AWM_RMAX]; \
-    __shared__ int awm_rc[AWM_RMAX]; __shared__ float awm_cnt[AWM_RMAX];                                                              \
+    __shared__ float awm_buf[LDSF]; __shared__ float awm_dp[PAIR_RMAX * 3]; __shared__ int awm_ri[PAIR_RMAX]; __shared__ int awm_rj[PAIR_RMAX]; \
+    __shared__ int awm_rc[PAIR_RMAX]; __shared__ float awm_cnt[PAIR_RMAX];                                                            \
     AwmLds L; L.buf = awm_buf; L.dp = awm_dp; L.rowI = awm_ri; L.rowJ = awm_rj; L.rowC = awm_rc; L.cnt = awm_cnt
 
-__device__ __forceinline__ bool awm_real(int id, int n0) { return id >= 0 && id < n0; }
 __device__ __forceinline__ bool awm_in(int softmax, bool real) { return softmax != AWM_SM_MASKED || real; }
-__device__ __forceinline__ float awm_act(int act, float z) { return act == 1 ? (z > 0.f ? z : 0.f) : act == 2 ? (z > 0.f ? z : 0.2f * z) : z; }
-// the activation's slope from its OUTPUT (h > 0 exactly where z > 0)
-__device__ __forceinline__ float awm_dact(int act, float h) { return act == 1 ? (h > 0.f ? 1.f : 0.f) : act == 2 ? (h > 0.f ? 1.f : 0.2f) : 1.f; }
 __device__ __forceinline__ void awm_ld4(const float* p, float (&v)[4])
 {
     const float4 t = *reinterpret_cast<const float4*>(p);
@@ -76,72 +68,27 @@ __device__ __forceinline__ void awm_ld4(const float* p, float (&v)[4])
 }
 __device__ __forceinline__ void awm_st4(float* p, const float (&v)[4]) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
 
-// the rows of a query trip: row r = (query i0 + r / K, neighbour r % K); rowI -1 on a row past the trip's pairs, rowJ the neighbour id (shadow: >= n0),
-// rowC the id of the query's centre row idx[i, 0];
-// dp (:381-382, the shadow point is the origin); cnt[qi] = the count behind 'mean' (:466-470)
-__device__ __forceinline__ void awm_rows_query(const AwmArgs& a, const AwmLds& L, int i0, int pad)
-{
-    for (int r = threadIdx.x; r < a.R; r += AWM_BLOCK) {
-        const int qi = r / a.K, k = r - qi * a.K, i = i0 + qi;
-        const bool valid = qi < a.tq && i < a.n;
-        int id = -1;
-        float d0 = 0.f, d1 = 0.f, d2 = 0.f;
-        if (valid) {
-            id = a.idx[(size_t)i * a.K + k];
-            float sx = 0.f, sy = 0.f, sz = 0.f;
-            if (awm_real(id, a.n0)) { sx = a.s[3 * (size_t)id]; sy = a.s[3 * (size_t)id + 1]; sz = a.s[3 * (size_t)id + 2]; }
-            d0 = (sx - a.q[3 * (size_t)i]) * a.inv_radius; d1 = (sy - a.q[3 * (size_t)i + 1]) * a.inv_radius; d2 = (sz - a.q[3 * (size_t)i + 2]) * a.inv_radius;
-        }
-        L.rowI[r] = valid ? i : -1; L.rowJ[r] = id; L.rowC[r] = valid ? a.idx[(size_t)i * a.K] : -1;
-        L.dp[3 * r] = d0; L.dp[3 * r + 1] = d1; L.dp[3 * r + 2] = d2;
-    }
-    for (int qi = threadIdx.x; qi < a.tq; qi += AWM_BLOCK) {
-        const int i = i0 + qi;
-        int cnt = 0;
-        if (i < a.n && a.red == AWM_MEAN)
-            for (int k = 0; k < a.K; k++) cnt += (a.idx[(size_t)i * a.K + k] < pad) ? 1 : 0;
-        L.cnt[qi] = (float)cnt;
-    }
-}
-
-// fc_0 and its activation: H[r][m] = act(y0), zero on the padding rows and columns — ONE expression for every pass ('max' compares recomputed products)
-__device__ __forceinline__ void awm_first_layer(const AwmArgs& a, const AwmLds& L, float* __restrict__ H)
-{
-#pragma unroll 4
-    for (int it = threadIdx.x; it < a.R * a.MP; it += AWM_BLOCK) {
-        const int r = it / a.MP, m = it - r * a.MP, i = L.rowI[r];
-        float v = 0.f;
-        if (i >= 0 && m < a.M) {
-            const int id = L.rowJ[r], c0 = L.rowC[r];
-            const float w0 = a.wp ? a.wp[m] : 0.f, w1 = a.wp ? a.wp[a.M + m] : 0.f, w2 = a.wp ? a.wp[2 * a.M + m] : 0.f;
-            const float ce = (a.cen && awm_real(c0, a.n0)) ? a.cen[(size_t)c0 * a.M + m] : 0.f;
-            const float nb = (a.nbr && awm_real(id, a.n0)) ? a.nbr[(size_t)id * a.M + m] : 0.f;
-            const float y0 = ((((L.dp[3 * r] * w0 + L.dp[3 * r + 1] * w1) + L.dp[3 * r + 2] * w2) + ce) + nb) + a.b0[m];
-            v = awm_act(a.act, y0);
-        }
-        H[r * a.LD + m] = v;
-    }
-}
-
-// One layer on MFMA, a wave per 16-row tile with every column tile's accumulator in registers.
+// One layer on MFMA, a wave per 16-row tile with every column tile's accumulator in registers: pair_mfma's loop and lane layout, written out.  As two calls
+// of pair_mfma the compiler re-evaluated the lanes' column test inside the k loop (one vector compare per MFMA) instead of keeping the nine masks, and the
+// passes at M = 72 and 144 measured 1.5 % to 4 % slower on the MI355X (profiles/pair_tile_refactor.md); this text compiles to the loop it always had.
 //   BACK false: out = act(in @ W + bias)          (in == out allowed: the tile's rows are read before they are written)
 //   BACK true : out = (in @ W^T) * act'(out)      (out holds the layer's input h on entry, the gradient at its pre-activation on exit)
-// A[i][k] in lane i + 16 k, B[k][j] in lane 16 k + j, D[4 (lane / 16) + v][lane % 16] in element v.  Columns past M read zero weights and are written as zero.
+// Columns past M read zero weights and are written as zero.
 template <bool BACK>
 __device__ __forceinline__ void awm_layer(const AwmArgs& a, const float* in, float* out, const float* __restrict__ W, const float* __restrict__ bias, int act)
 {
     const int wave = threadIdx.x / CBL_WAVE, lane = threadIdx.x % CBL_WAVE, li = lane % 16, lk = lane / 16;
-    for (int t = wave; t < a.R / 16; t += AWM_WAVES) {
-        awm_f32x4 acc[AWM_NCT];
+    for (int t = wave; t < a.R / 16; t += PAIR_WAVES) {
+        pair_f32x4 acc[PAIR_NCT];
 #pragma unroll
-        for (int c = 0; c < AWM_NCT; c++) acc[c] = awm_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int c = 0; c < PAIR_NCT; c++) acc[c] = pair_f32x4{0.f, 0.f, 0.f, 0.f};
         const float* arow = in + (16 * t + li) * a.LD;
 #pragma unroll 4
         for (int k0 = 0; k0 < a.MP; k0 += 4) {                             // (MP / 4 is a multiple of 4: no remainder loop; four steps' loads in flight)
             const int kk = k0 + lk;
             const float av = arow[kk];
 #pragma unroll
-            for (int c = 0; c < AWM_NCT; c++) {
+            for (int c = 0; c < PAIR_NCT; c++) {
                 if (c >= a.nct) continue;
                 const int col = 16 * c + li;
                 const float bv = (kk < a.M && col < a.M) ? (BACK ? W[(size_t)col * a.M + kk] : W[(size_t)kk * a.M + col]) : 0.f;
@@ -149,24 +96,25 @@ __device__ __forceinline__ void awm_layer(const AwmArgs& a, const float* in, flo
             }
         }
 #pragma unroll
-        for (int c = 0; c < AWM_NCT; c++) {
+        for (int c = 0; c < PAIR_NCT; c++) {
             if (c >= a.nct) continue;
             const int col = 16 * c + li;
 #pragma unroll
             for (int v = 0; v < 4; v++) {
                 float* o = out + (16 * t + 4 * lk + v) * a.LD + col;
                 float val = 0.f;
-                if (col < a.M) val = BACK ? acc[c][v] * awm_dact(act, *o) : awm_act(act, acc[c][v] + bias[col]);
+                if (col < a.M) val = BACK ? acc[c][v] * pair_dact(act, *o) : pair_act(act, acc[c][v] + bias[col]);
                 *o = val;
             }
         }
     }
 }
 
-// rows -> y: fc_0 into buffer 0, then the layers; keep: layer l writes buffer l (the backward pass reads every h), otherwise in place.  Ends behind a barrier.
+// rows -> y: fc_0 and its activation into buffer 0 (act(y0 + b0)), then the layers; keep: layer l writes buffer l (the backward pass reads every h),
+// otherwise in place.  Ends behind a barrier.
 __device__ __forceinline__ float* awm_chain(const AwmArgs& a, const AwmLds& L, bool keep)
 {
-    awm_first_layer(a, L, L.buf);
+    pair_fold_rows(a, L, a.M, a.MP, a.wp, a.cen, a.nbr, L.buf, a.LD, [&](int m, float y0) { return pair_act(a.act, y0 + a.b0[m]); });
     __syncthreads();
     float* in = L.buf;
     for (int l = 1; l <= a.layers; l++) {
@@ -196,21 +144,21 @@ __device__ __forceinline__ void awm_walk_back(const AwmArgs& a, const AwmLds& L,
 __device__ __forceinline__ void awm_weights_query(const AwmArgs& a, const AwmLds& L, int i0, float* Y, float* __restrict__ lse_out)
 {
     if (a.softmax == AWM_SM_NONE) return;
-    for (int it = threadIdx.x; it < a.tq * a.M; it += AWM_BLOCK) {
+    for (int it = threadIdx.x; it < a.tq * a.M; it += PAIR_BLOCK) {
         const int qi = it / a.M, m = it - qi * a.M, i = i0 + qi;
         if (i >= a.n) continue;
         float* col = Y + (size_t)qi * a.K * a.LD + m;
         const int* rj = L.rowJ + qi * a.K;
         float mx = -INFINITY, sm = 0.f;
         for (int k = 0; k < a.K; k++) {
-            if (!awm_in(a.softmax, awm_real(rj[k], a.n0))) continue;
+            if (!awm_in(a.softmax, pair_real(rj[k], a.n0))) continue;
             const float y = col[k * a.LD];
             if (y > mx) { sm = sm * expf(mx - y) + 1.f; mx = y; }
             else sm += expf(y - mx);
         }
         const float lse = mx + logf(sm);                                 // (empty domain: -inf, never read)
         if (lse_out) lse_out[(size_t)i * a.M + m] = lse;
-        for (int k = 0; k < a.K; k++) col[k * a.LD] = awm_in(a.softmax, awm_real(rj[k], a.n0)) ? expf(col[k * a.LD] - lse) : 0.f;
+        for (int k = 0; k < a.K; k++) col[k * a.LD] = awm_in(a.softmax, pair_real(rj[k], a.n0)) ? expf(col[k * a.LD] - lse) : 0.f;
     }
 }
 
@@ -218,7 +166,7 @@ __device__ __forceinline__ void awm_weights_query(const AwmArgs& a, const AwmLds
 __device__ __forceinline__ float awm_da(const AwmArgs& a, const AwmBwd& b, size_t at, float sc, float wf)
 {
     const float g = b.go[at];
-    if (a.red != AWM_MAX) return g * sc;
+    if (a.red != PAIR_MAX) return g * sc;
     const float tc = b.ties[at];
     return (wf == b.out[at] && tc > 0.f) ? g / tc : 0.f;
 }
@@ -234,38 +182,38 @@ __device__ __forceinline__ float awm_dw(const AwmArgs& a, const AwmBwd& b, int i
 
 // ---------------------------------------------------------------- F
 template <int LDSF>
-__global__ __launch_bounds__(AWM_BLOCK) void awm_forward_kernel(AwmArgs a, float* __restrict__ out)
+__global__ __launch_bounds__(PAIR_BLOCK) void awm_forward_kernel(AwmArgs a, float* __restrict__ out)
 {
     AWM_LDS_DECL(L);
-    const int pad = (a.red == AWM_MEAN) ? *a.padding_num : 0;
+    const int pad = (a.red == PAIR_MEAN) ? *a.padding_num : 0;
     const int ntrips = (a.n + a.tq - 1) / a.tq, U = a.C / 4;
     for (int trip = blockIdx.x; trip < ntrips; trip += gridDim.x) {
         const int i0 = trip * a.tq;
-        awm_rows_query(a, L, i0, pad);
+        pair_rows_query(a, L, i0, pad);
         __syncthreads();
         float* Y = awm_chain(a, L, false);
         awm_weights_query(a, L, i0, Y, nullptr);
         __syncthreads();
-        for (int it = threadIdx.x; it < a.tq * U; it += AWM_BLOCK) {
+        for (int it = threadIdx.x; it < a.tq * U; it += PAIR_BLOCK) {
             const int qi = it / U, c0 = 4 * (it - qi * U), i = i0 + qi;
             if (i >= a.n) continue;
             int me[4];
             float acc[4];
 #pragma unroll
-            for (int e = 0; e < 4; e++) { me[e] = (c0 + e) / a.S; acc[e] = a.red == AWM_MAX ? -INFINITY : 0.f; }
+            for (int e = 0; e < 4; e++) { me[e] = (c0 + e) / a.S; acc[e] = a.red == PAIR_MAX ? -INFINITY : 0.f; }
 #pragma unroll 4
             for (int k = 0; k < a.K; k++) {
                 const int r = qi * a.K + k, id = L.rowJ[r];
-                const bool real = awm_real(id, a.n0);
+                const bool real = pair_real(id, a.n0);
                 float f4[4] = {0.f, 0.f, 0.f, 0.f};
                 if (real) awm_ld4(a.f + (size_t)id * a.C + c0, f4);
 #pragma unroll
                 for (int e = 0; e < 4; e++) {
-                    const float av = real ? Y[r * a.LD + me[e]] * f4[e] : (a.red == AWM_MAX ? AWM_SHADOW_MAX : 0.f);      // :458, :475-477
-                    if (a.red == AWM_MAX) acc[e] = av > acc[e] ? av : acc[e]; else acc[e] += av;
+                    const float av = real ? Y[r * a.LD + me[e]] * f4[e] : (a.red == PAIR_MAX ? AWM_SHADOW_MAX : 0.f);      // :458, :475-477
+                    if (a.red == PAIR_MAX) acc[e] = av > acc[e] ? av : acc[e]; else acc[e] += av;
                 }
             }
-            if (a.red == AWM_MEAN) {
+            if (a.red == PAIR_MEAN) {
                 const float nn = L.cnt[qi] + 1e-5f;                      // :466-470
 #pragma unroll
                 for (int e = 0; e < 4; e++) acc[e] = acc[e] / nn;
@@ -279,27 +227,26 @@ __global__ __launch_bounds__(AWM_BLOCK) void awm_forward_kernel(AwmArgs a, float
 // ---------------------------------------------------------------- BQ
 // partial: this workgroup's fp32 sums, [layers M M | 3 M grad_w_pos | M grad_bias0 | layers M grad_hidden_b] (PS floats per workgroup)
 template <int LDSF>
-__global__ __launch_bounds__(AWM_BLOCK) void awm_bwd_query_kernel(AwmArgs a, AwmBwd b, float* __restrict__ grad_center, float* __restrict__ partial, size_t PS)
+__global__ __launch_bounds__(PAIR_BLOCK) void awm_bwd_query_kernel(AwmArgs a, AwmBwd b, float* __restrict__ grad_center, float* __restrict__ partial, size_t PS)
 {
     AWM_LDS_DECL(L);
-    const int pad = (a.red == AWM_MEAN) ? *a.padding_num : 0;
+    const int pad = (a.red == PAIR_MEAN) ? *a.padding_num : 0;
     const int ntrips = (a.n + a.tq - 1) / a.tq, U = a.C / 4;
     const bool sm = a.softmax != AWM_SM_NONE;
-    const int wave = threadIdx.x / CBL_WAVE, lane = threadIdx.x % CBL_WAVE, li = lane % 16, lk = lane / 16;
     float* mine = partial ? partial + (size_t)blockIdx.x * PS : nullptr;
     double gb[3] = {0.0, 0.0, 0.0}, T[3] = {0.0, 0.0, 0.0};             // thread m < M: the column sums of dz at layer 0, 1, 2 and of dp^T dz0
     for (int trip = blockIdx.x; trip < ntrips; trip += gridDim.x) {
         const int i0 = trip * a.tq;
         const bool first = trip == (int)blockIdx.x;
-        awm_rows_query(a, L, i0, pad);
+        pair_rows_query(a, L, i0, pad);
         __syncthreads();
         float* Y = awm_chain(a, L, true);
         awm_weights_query(a, L, i0, Y, b.lse);
-        for (int qi = threadIdx.x; qi < a.tq; qi += AWM_BLOCK)
-            if (i0 + qi < a.n) b.inv_nn[i0 + qi] = a.red == AWM_MEAN ? 1.0f / (L.cnt[qi] + 1e-5f) : 1.0f;
+        for (int qi = threadIdx.x; qi < a.tq; qi += PAIR_BLOCK)
+            if (i0 + qi < a.n) b.inv_nn[i0 + qi] = a.red == PAIR_MEAN ? 1.0f / (L.cnt[qi] + 1e-5f) : 1.0f;
         __syncthreads();
-        if (a.red == AWM_MAX) {                                          // how many pairs attain each maximum
-            for (int it = threadIdx.x; it < a.tq * U; it += AWM_BLOCK) {
+        if (a.red == PAIR_MAX) {                                          // how many pairs attain each maximum
+            for (int it = threadIdx.x; it < a.tq * U; it += PAIR_BLOCK) {
                 const int qi = it / U, c0 = 4 * (it - qi * U), i = i0 + qi;
                 if (i >= a.n) continue;
                 int me[4];
@@ -309,7 +256,7 @@ __global__ __launch_bounds__(AWM_BLOCK) void awm_bwd_query_kernel(AwmArgs a, Awm
                 for (int e = 0; e < 4; e++) me[e] = (c0 + e) / a.S;
                 for (int k = 0; k < a.K; k++) {
                     const int r = qi * a.K + k, id = L.rowJ[r];
-                    const bool real = awm_real(id, a.n0);
+                    const bool real = pair_real(id, a.n0);
                     float f4[4] = {0.f, 0.f, 0.f, 0.f};
                     if (real) awm_ld4(a.f + (size_t)id * a.C + c0, f4);
 #pragma unroll
@@ -320,7 +267,7 @@ __global__ __launch_bounds__(AWM_BLOCK) void awm_bwd_query_kernel(AwmArgs a, Awm
             __syncthreads();
         }
         // w -> dy in place: dw per pair, D = sum_k w dw, dy = w (dw - D) formed per pair (a query with one real neighbour has dy = 0 exactly)
-        for (int it = threadIdx.x; it < a.tq * a.MP; it += AWM_BLOCK) {
+        for (int it = threadIdx.x; it < a.tq * a.MP; it += PAIR_BLOCK) {
             const int qi = it / a.MP, m = it - qi * a.MP, i = i0 + qi;
             float* col = Y + (size_t)qi * a.K * a.LD + m;
             if (i >= a.n || m >= a.M) {
@@ -328,45 +275,27 @@ __global__ __launch_bounds__(AWM_BLOCK) void awm_bwd_query_kernel(AwmArgs a, Awm
                 continue;
             }
             const int* rj = L.rowJ + qi * a.K;
-            const float sc = a.red == AWM_MEAN ? 1.0f / (L.cnt[qi] + 1e-5f) : 1.0f;
+            const float sc = a.red == PAIR_MEAN ? 1.0f / (L.cnt[qi] + 1e-5f) : 1.0f;
             float D = 0.f;
             if (sm) {
                 for (int k = 0; k < a.K; k++)
-                    if (awm_real(rj[k], a.n0)) D += col[k * a.LD] * awm_dw(a, b, i, rj[k], m, sc, col[k * a.LD]);
+                    if (pair_real(rj[k], a.n0)) D += col[k * a.LD] * awm_dw(a, b, i, rj[k], m, sc, col[k * a.LD]);
                 b.D[(size_t)i * a.M + m] = D;
             }
             for (int k = 0; k < a.K; k++) {
-                const bool real = awm_real(rj[k], a.n0);
+                const bool real = pair_real(rj[k], a.n0);
                 const float w = col[k * a.LD];
                 const float dw = real ? awm_dw(a, b, i, rj[k], m, sc, w) : 0.f;
                 col[k * a.LD] = sm ? (awm_in(a.softmax, real) ? w * (dw - D) : 0.f) : dw;
             }
         }
-        for (int it = a.tq * a.K * a.MP + threadIdx.x; it < a.R * a.MP; it += AWM_BLOCK)       // the rows behind the last query: no gradient
+        for (int it = a.tq * a.K * a.MP + threadIdx.x; it < a.R * a.MP; it += PAIR_BLOCK)       // the rows behind the last query: no gradient
             Y[(it / a.MP) * a.LD + it % a.MP] = 0.f;
         __syncthreads();
         awm_walk_back(a, L, [&](int l, const float* h, const float* dz) {
             if (!mine) return;
-            // grad_hidden_w[l-1][p][c] += sum_r h[r][p] dz[r][c]: tile (tp, tc) of wave (tp nct + tc) % 4, continued from the workgroup's own partial
-            float* pw = mine + (size_t)(l - 1) * a.M * a.M;
-            for (int tile = wave; tile < a.nct * a.nct; tile += AWM_WAVES) {
-                const int tp = tile / a.nct, tc = tile - tp * a.nct, col = 16 * tc + li;
-                awm_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-                if (!first) {
-#pragma unroll
-                    for (int v = 0; v < 4; v++) {
-                        const int p = 16 * tp + 4 * lk + v;
-                        if (p < a.M && col < a.M) acc[v] = pw[(size_t)p * a.M + col];
-                    }
-                }
-                for (int r0 = 0; r0 < a.R; r0 += 4)
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(h[(r0 + lk) * a.LD + 16 * tp + li], dz[(r0 + lk) * a.LD + col], acc, 0, 0, 0);
-#pragma unroll
-                for (int v = 0; v < 4; v++) {
-                    const int p = 16 * tp + 4 * lk + v;
-                    if (p < a.M && col < a.M) pw[(size_t)p * a.M + col] = acc[v];
-                }
-            }
+            // grad_hidden_w[l-1][p][c] += sum_r h[r][p] dz[r][c]
+            pair_wgrad(a.R, a.nct, a.M, [&](int r, int p) { return h[r * a.LD + p]; }, dz, a.LD, a.nct, a.M, mine + (size_t)(l - 1) * a.M * a.M, a.M, 0, first);
             if ((int)threadIdx.x < a.M) {
                 float s = 0.f;
                 for (int r = 0; r < a.R; r++) s += dz[r * a.LD + threadIdx.x];
@@ -376,7 +305,7 @@ __global__ __launch_bounds__(AWM_BLOCK) void awm_bwd_query_kernel(AwmArgs a, Awm
         });
         // dz0 in buffer 0
         if (grad_center) {
-            for (int it = threadIdx.x; it < a.tq * a.M; it += AWM_BLOCK) {
+            for (int it = threadIdx.x; it < a.tq * a.M; it += PAIR_BLOCK) {
                 const int qi = it / a.M, m = it - qi * a.M, i = i0 + qi;
                 if (i >= a.n) continue;
                 float s = 0.f;
@@ -423,7 +352,7 @@ __global__ __launch_bounds__(256) void awm_finalize_kernel(int M, int layers, in
 
 // ---------------------------------------------------------------- BT
 template <int LDSF>
-__global__ __launch_bounds__(AWM_BLOCK) void awm_bwd_target_kernel(AwmArgs a, AwmBwd b, CblFastDiv dvK, const int* __restrict__ order,
+__global__ __launch_bounds__(PAIR_BLOCK) void awm_bwd_target_kernel(AwmArgs a, AwmBwd b, CblFastDiv dvK, const int* __restrict__ order,
                                                                    const int* __restrict__ inv_start, const int* __restrict__ inv_src,
                                                                    float* __restrict__ grad_neighbor, float* __restrict__ grad_value)
 {
@@ -436,36 +365,23 @@ __global__ __launch_bounds__(AWM_BLOCK) void awm_bwd_target_kernel(AwmArgs a, Aw
         int ce = e_lo;
         do {                                                             // chunks of R pairs; at least one, so that a target without pairs is stored too
             const bool last = ce + a.R >= e_hi;
-            for (int r = threadIdx.x; r < a.R; r += AWM_BLOCK) {
-                const int e = ce + r;
-                int i = -1, j = -1;
-                float d0 = 0.f, d1 = 0.f, d2 = 0.f;
-                if (e < e_hi) {
-                    const int p = inv_src[e];
-                    i = (int)cbl_fastdiv((unsigned)p, dvK);
-                    j = a.idx[p];
-                    d0 = (a.s[3 * (size_t)j] - a.q[3 * (size_t)i]) * a.inv_radius; d1 = (a.s[3 * (size_t)j + 1] - a.q[3 * (size_t)i + 1]) * a.inv_radius;
-                    d2 = (a.s[3 * (size_t)j + 2] - a.q[3 * (size_t)i + 2]) * a.inv_radius;
-                }
-                L.rowI[r] = i; L.rowJ[r] = j; L.rowC[r] = i >= 0 ? a.idx[(size_t)i * a.K] : -1;
-                L.dp[3 * r] = d0; L.dp[3 * r + 1] = d1; L.dp[3 * r + 2] = d2;
-            }
+            pair_rows_target(a, L, dvK, inv_src, ce, e_hi);
             __syncthreads();
             float* Y = awm_chain(a, L, walk);
             if (sm) {
-                for (int it = threadIdx.x; it < a.R * a.M; it += AWM_BLOCK) {
+                for (int it = threadIdx.x; it < a.R * a.M; it += PAIR_BLOCK) {
                     const int r = it / a.M, m = it - r * a.M, i = L.rowI[r];
                     if (i >= 0) Y[r * a.LD + m] = expf(Y[r * a.LD + m] - b.lse[(size_t)i * a.M + m]);
                 }
                 __syncthreads();
             }
             if (grad_value) {                                            // grad_features_value[j, c] = sum over j's pairs of da w
-                for (int it = threadIdx.x; it < a.tpt * U; it += AWM_BLOCK) {
+                for (int it = threadIdx.x; it < a.tpt * U; it += PAIR_BLOCK) {
                     const int tl = it / U, c0 = 4 * (it - tl * U), tr = t_lo + tl;
                     if (tr >= t_hi) continue;
                     const int s0 = inv_start[tr], s1 = inv_start[tr + 1];
-                    const bool begins = s0 >= ce && (s0 < ce + a.R || last);
-                    if (!begins && !(s0 < ce && s1 > ce)) continue;
+                    bool begins;
+                    if (!pair_target_in_chunk(s0, s1, ce, a.R, last, &begins)) continue;
                     const int j = order ? order[tr] : tr;
                     int me[4];
                     float acc[4] = {0.f, 0.f, 0.f, 0.f}, f4[4];
@@ -493,7 +409,7 @@ __global__ __launch_bounds__(AWM_BLOCK) void awm_bwd_target_kernel(AwmArgs a, Aw
             }
             if (walk) {
                 __syncthreads();
-                for (int it = threadIdx.x; it < a.R * a.MP; it += AWM_BLOCK) {      // w -> dy in place
+                for (int it = threadIdx.x; it < a.R * a.MP; it += PAIR_BLOCK) {      // w -> dy in place
                     const int r = it / a.MP, m = it - r * a.MP, i = L.rowI[r];
                     float dy = 0.f;
                     if (i >= 0 && m < a.M) {
@@ -505,18 +421,7 @@ __global__ __launch_bounds__(AWM_BLOCK) void awm_bwd_target_kernel(AwmArgs a, Aw
                 }
                 __syncthreads();
                 awm_walk_back(a, L, [](int, const float*, const float*) {});
-                for (int it = threadIdx.x; it < a.tpt * a.M; it += AWM_BLOCK) {     // grad_neighbor[j, m] = sum over j's pairs of dz0
-                    const int tl = it / a.M, m = it - tl * a.M, tr = t_lo + tl;
-                    if (tr >= t_hi) continue;
-                    const int s0 = inv_start[tr], s1 = inv_start[tr + 1];
-                    const bool begins = s0 >= ce && (s0 < ce + a.R || last);
-                    if (!begins && !(s0 < ce && s1 > ce)) continue;
-                    const int j = order ? order[tr] : tr;
-                    float s = 0.f;
-                    for (int e = max(s0, ce); e < min(s1, ce + a.R); e++) s += L.buf[(e - ce) * a.LD + m];
-                    float* dst = grad_neighbor + (size_t)j * a.M + m;
-                    *dst = begins ? s : *dst + s;
-                }
+                pair_target_sum(a, a.M, L.buf, a.LD, t_lo, t_hi, ce, last, order, inv_start, grad_neighbor);      // grad_neighbor[j, m] = sum over j's pairs of dz0
             }
             __syncthreads();
             ce += a.R;
@@ -528,7 +433,7 @@ __global__ __launch_bounds__(AWM_BLOCK) void awm_bwd_target_kernel(AwmArgs a, Aw
 int awm_check(int n, int n0, int K, int C, int M, int layers, float radius, int softmax, int reduction)
 {
     if (n < 0 || n0 < 0 || K <= 0 || C <= 0 || M <= 0 || layers < 0 || !(radius > 0.f)) return CBL_ERR_BAD_ARG;
-    if (softmax < 0 || softmax > AWM_SM_UNMASK || reduction < 0 || reduction > AWM_MAX) return CBL_ERR_BAD_ARG;
+    if (softmax < 0 || softmax > AWM_SM_UNMASK || reduction < 0 || reduction > PAIR_MAX) return CBL_ERR_BAD_ARG;
     if (layers < 1 || layers > 2 || K > AWM_KMAX || C % 4 != 0 || C > AWM_CMAX || C % M != 0) return CBL_ERR_UNSUPPORTED;
     if (M < AWM_MMIN || M > AWM_MMAX || (K > AWM_KWIDE && M > AWM_MNARROW)) return CBL_ERR_UNSUPPORTED;
     const int S = C / M;
@@ -542,40 +447,26 @@ inline int awm_plan(int LD, int nbuf, int need, int want, int* rows)
     const int sizes[3] = {AWM_LDS0, AWM_LDS1, AWM_LDS2};
     for (int pass = 0; pass < 2; pass++)
         for (int z = 0; z < 3; z++) {
-            int r = sizes[z] / (nbuf * LD) / 16 * 16;
-            if (r > AWM_RMAX) r = AWM_RMAX;
+            const int r = pair_rows_fit(sizes[z], nbuf * LD);
             if (r >= (pass == 0 ? want : need)) { *rows = r; return z; }
         }
     *rows = 0;
     return -1;
 }
-inline int awm_up16(int v) { return (v + 15) / 16 * 16; }
-// rows of MP + 4 floats (the 16 rows an MFMA operand reads then fall into 16 different groups of 4 banks) where a tile still fits, MP where not
-inline int awm_plan_rows(AwmArgs& a, int nbuf, int need, int want, int* rows)
+// the plan of pair_plan_query / pair_plan_target for `nbuf` row buffers: rows of MP + 4 floats (the 16 rows an MFMA operand reads then fall into 16
+// different groups of 4 banks) where a tile still fits, MP where not.  The callable writes the pitch it chose into a.LD: use it within the expression
+// that makes it, on the args object that is launched
+inline auto awm_plan_rows(AwmArgs& a, int nbuf)
 {
-    a.LD = a.MP + 4;
-    int z = awm_plan(a.LD, nbuf, need, want, rows);
-    if (z < 0) { a.LD = a.MP; z = awm_plan(a.LD, nbuf, need, want, rows); }
-    return z;
-}
-// a query pass: as many whole queries as the rows hold
-inline int awm_plan_query(AwmArgs& a, int nbuf)
-{
-    int rows;
-    const int z = awm_plan_rows(a, nbuf, awm_up16(a.K), awm_up16(a.K) > 64 ? awm_up16(a.K) : 64, &rows);
-    if (z < 0) return z;
-    a.tq = rows / a.K;
-    if (a.n > 0 && a.tq > a.n) a.tq = a.n;
-    a.R = awm_up16(a.tq * a.K);
-    return z;
+    return [&a, nbuf](int need, int want, int* rows) {
+        a.LD = a.MP + 4;
+        int z = awm_plan(a.LD, nbuf, need, want, rows);
+        if (z < 0) { a.LD = a.MP; z = awm_plan(a.LD, nbuf, need, want, rows); }
+        return z;
+    };
 }
 
-inline size_t awm_up(size_t b) { return (b + 255) & ~(size_t)255; }
-inline int awm_bq_blocks(size_t PS)
-{
-    const size_t fit = (size_t)AWM_BQ_PARTIAL / PS;
-    return fit > (size_t)AWM_BQ_BLOCKS ? AWM_BQ_BLOCKS : fit < (size_t)AWM_BQ_BLOCKS_MIN ? AWM_BQ_BLOCKS_MIN : (int)fit;
-}
+inline int awm_bq_blocks(size_t PS) { return pair_bq_blocks(PS, AWM_BQ_BLOCKS, AWM_BQ_BLOCKS_MIN); }
 struct AwmSpace { size_t partial, lse, D, inv_nn, ties, total, PS; };
 inline AwmSpace awm_space(int n, int C, int M, int layers)
 {
@@ -583,11 +474,11 @@ inline AwmSpace awm_space(int n, int C, int M, int layers)
     AwmSpace s;
     s.PS = (size_t)layers * M * M + (size_t)(4 + layers) * M;
     s.partial = 0;
-    s.lse = awm_up(sizeof(float) * (size_t)awm_bq_blocks(s.PS) * s.PS);
-    s.D = s.lse + awm_up(sizeof(float) * rows * M);
-    s.inv_nn = s.D + awm_up(sizeof(float) * rows * M);
-    s.ties = s.inv_nn + awm_up(sizeof(float) * rows);
-    s.total = s.ties + awm_up(sizeof(float) * rows * C);
+    s.lse = pair_up256(sizeof(float) * (size_t)awm_bq_blocks(s.PS) * s.PS);
+    s.D = s.lse + pair_up256(sizeof(float) * rows * M);
+    s.inv_nn = s.D + pair_up256(sizeof(float) * rows * M);
+    s.ties = s.inv_nn + pair_up256(sizeof(float) * rows);
+    s.total = s.ties + pair_up256(sizeof(float) * rows * C);
     return s;
 }
 
@@ -596,7 +487,7 @@ inline AwmArgs awm_args(int n, int n0, int K, int C, int M, int layers, int act,
                         const int* padding_num)
 {
     AwmArgs a;
-    a.n = n; a.n0 = n0; a.K = K; a.C = C; a.M = M; a.S = C / M; a.MP = awm_up16(M); a.LD = a.MP; a.nct = a.MP / 16; a.layers = layers; a.act = act;
+    a.n = n; a.n0 = n0; a.K = K; a.C = C; a.M = M; a.S = C / M; a.MP = pair_up16(M); a.LD = a.MP; a.nct = a.MP / 16; a.layers = layers; a.act = act;
     a.softmax = softmax; a.red = red; a.R = 16; a.tq = 1; a.tpt = 1;
     a.q = q; a.s = s; a.idx = idx; a.f = f; a.cen = cen; a.nbr = nbr; a.wp = wp; a.b0 = b0; a.hw = hw; a.hb = hb; a.inv_radius = 1.0f / radius;
     a.padding_num = padding_num;
@@ -605,12 +496,7 @@ inline AwmArgs awm_args(int n, int n0, int K, int C, int M, int layers, int act,
 
 }  // namespace
 
-#define AWM_LAUNCH(kernel, z, grid, st, ...)                                                                                         \
-    do {                                                                                                                             \
-        if ((z) == 0) hipLaunchKernelGGL(kernel<AWM_LDS0>, grid, dim3(AWM_BLOCK), 0, st, __VA_ARGS__);                               \
-        else if ((z) == 1) hipLaunchKernelGGL(kernel<AWM_LDS1>, grid, dim3(AWM_BLOCK), 0, st, __VA_ARGS__);                          \
-        else hipLaunchKernelGGL(kernel<AWM_LDS2>, grid, dim3(AWM_BLOCK), 0, st, __VA_ARGS__);                                        \
-    } while (0)
+#define AWM_LAUNCH(kernel, z, ...) PAIR_LAUNCH(kernel, z, AWM_LDS0, AWM_LDS1, AWM_LDS2, __VA_ARGS__)
 
 CBL_EXPORT size_t cbl_adaptive_weight_mlp_workspace_bytes(int n, int n0, int K, int C, int M, int layers)
 {
@@ -629,12 +515,12 @@ CBL_EXPORT int cbl_adaptive_weight_mlp_forward(int n, int n0, int K, int C, int 
     if (rc) return rc;
     if (n == 0) return CBL_OK;
     if (!query_points || !support_points || !neighbors_indices || !features || !bias || !hidden_w || !hidden_b || !out ||
-        (reduction == AWM_MEAN && !padding_num)) return CBL_ERR_BAD_ARG;
+        (reduction == PAIR_MEAN && !padding_num)) return CBL_ERR_BAD_ARG;
     if (!cbl_host_aligned16(features) || !cbl_host_aligned16(out)) return CBL_ERR_UNSUPPORTED;
     hipStream_t st = cbl_stream(stream);
     AwmArgs a = awm_args(n, n0, K, C, M, layers, activation, query_points, support_points, neighbors_indices, features, center_term, neighbor_term, w_pos, bias,
                          hidden_w, hidden_b, radius, softmax, reduction, padding_num);
-    const int z = awm_plan_query(a, 1);
+    const int z = pair_plan_query(a, awm_plan_rows(a, 1));
     if (z < 0) return CBL_ERR_UNSUPPORTED;
     AWM_LAUNCH(awm_forward_kernel, z, dim3(cbl_grid_for(n, a.tq, AWM_F_BLOCKS)), st, a, out);
     return cbl_status();
@@ -652,7 +538,7 @@ CBL_EXPORT int cbl_adaptive_weight_mlp_backward_csr(int n, int n0, int K, int C,
     if (rc) return rc;
     if (!grad_features_value && !grad_center && !grad_neighbor && !grad_w_pos && !grad_bias && !grad_hidden_w && !grad_hidden_b) return CBL_OK;
     if (n > 0 && (!query_points || !support_points || !neighbors_indices || !features || !bias || !hidden_w || !hidden_b || !grad_out ||
-                  (reduction == AWM_MEAN && !padding_num) || (reduction == AWM_MAX && !out))) return CBL_ERR_BAD_ARG;
+                  (reduction == PAIR_MEAN && !padding_num) || (reduction == PAIR_MAX && !out))) return CBL_ERR_BAD_ARG;
     const bool table = (grad_features_value || grad_neighbor) && n0 > 0;
     if (table && (!inv_start || !inv_src || !support_points || !features)) return CBL_ERR_BAD_ARG;
     if (!workspace || !cbl_host_aligned16(workspace)) return CBL_ERR_BAD_ARG;
@@ -679,7 +565,7 @@ CBL_EXPORT int cbl_adaptive_weight_mlp_backward_csr(int n, int n0, int K, int C,
     b.lse = reinterpret_cast<float*>(base + sp.lse); b.D = reinterpret_cast<float*>(base + sp.D);
     b.inv_nn = reinterpret_cast<float*>(base + sp.inv_nn); b.ties = reinterpret_cast<float*>(base + sp.ties);
     const bool sums = grad_w_pos || grad_bias || grad_hidden_w || grad_hidden_b;
-    const int zq = awm_plan_query(a, layers + 1);
+    const int zq = pair_plan_query(a, awm_plan_rows(a, layers + 1));
     if (zq < 0) return CBL_ERR_UNSUPPORTED;
     const unsigned gq = cbl_grid_for(n, a.tq, awm_bq_blocks(sp.PS));
     AWM_LAUNCH(awm_bwd_query_kernel, zq, dim3(gq), st, a, b, grad_center, sums ? partial : (float*)nullptr, sp.PS);
@@ -687,14 +573,8 @@ CBL_EXPORT int cbl_adaptive_weight_mlp_backward_csr(int n, int n0, int K, int C,
         hipLaunchKernelGGL(awm_finalize_kernel, dim3(cbl_grid_for((long long)sp.PS, 256, 256)), dim3(256), 0, st, M, layers, (int)gq, sp.PS, (const float*)partial,
                            grad_hidden_w, grad_w_pos, grad_bias, grad_hidden_b, softmax != AWM_SM_NONE ? 1 : 0);
     if (table) {
-        // a trip's targets: about one tile of pairs at the table's mean segment length (the chunk loop takes whatever a trip really has)
-        int rows;
-        const int zt = awm_plan_rows(a, grad_neighbor ? layers + 1 : 1, 16, 128, &rows);
+        const int zt = pair_plan_target(a, awm_plan_rows(a, grad_neighbor ? layers + 1 : 1));
         if (zt < 0) return CBL_ERR_UNSUPPORTED;
-        a.R = rows;
-        const long long mean = ((long long)n * K + n0 - 1) / n0;
-        long long tpt = rows / (mean > 0 ? mean : 1);
-        a.tpt = (int)(tpt < 1 ? 1 : tpt > AWM_TPT_MAX ? AWM_TPT_MAX : tpt);
         AWM_LAUNCH(awm_bwd_target_kernel, zt, dim3(cbl_grid_for(n0, a.tpt, AWM_BT_BLOCKS)), st, a, b, cbl_fastdiv_make((unsigned)K), order_dst, inv_start,
                    inv_src, grad_neighbor, grad_features_value);
     }

@@ -8,13 +8,13 @@
 //     out[i] = reduce_k mask[i,k] * h_L                                                               sum | mean (:609-613) | max (a shadow pair counts as 0)
 // Shadow pairs go through every layer and every statistic; only the final mask removes them.
 //
-// MI355X mapping (the decision of adaptive_weight_mlp.hip).  A workgroup of four waves takes a tile of whole queries per trip: R = their pair rows padded to a
-// multiple of 16, H zero-padded to HP = a multiple of 16 inside the kernel.  LDS holds xh_l of the hidden layers (L buffers R x LDH), one column tile of the
-// last layer (R x CT, CT = 16 / 32 / 64 columns: the (R, C_out) product is never held whole) and, in the backward passes, one R x LDH gradient buffer.
-//   y_0      : VALU, one thread per (row, column), ONE expression for every pass
-//   layers   : chains of v_mfma_f32_16x16x4_f32 (an exact fp32 fmaf chain: a pair recomputes to the same bits in every sweep and on the target side, which
-//              'max' relies on); the A operand is h_l = act(gamma xh + beta) formed from the stored xh at the load, gamma = beta = 0 in the padded columns,
-//              so these stay exactly zero whatever beta is; the weights are the B operand from global memory (L1 / L2 resident)
+// MI355X mapping.  A workgroup of four waves takes a tile of whole queries per trip: R = their pair rows padded to a multiple of 16, H zero-padded to HP = a
+// multiple of 16 inside the kernel.  The row convention, the y_0 fold, the MFMA product and weight-gradient tiles, the target-side chunk walk and the
+// host-side tile planning are pair_tile.h's, shared with adaptive_weight_mlp.hip.  LDS holds xh_l of the hidden layers (L buffers R x LDH), one column tile
+// of the last layer (R x CT, CT = 16 / 32 / 64 columns: the (R, C_out) product is never held whole) and, in the backward passes, one R x LDH gradient buffer.
+//   layers   : a pair recomputes to the same bits in every sweep and on the target side, which 'max' relies on; the A operand is h_l = act(gamma xh + beta)
+//              formed from the stored xh at the load, gamma = beta = 0 in the padded columns, so these stay exactly zero whatever beta is; the weights are
+//              the B operand from global memory (L1 / L2 resident)
 //   sums     : per column over the tile's REAL rows (rowI >= 0; padding rows and padded columns enter no statistic), fp64 per thread, combined through LDS in a
 //              fixed order and added to the workgroup's own fp64 partial in the workspace; finalize kernels add the partials in workgroup order (fp64)
 // With batch statistics layer l + 1 cannot be formed before the statistics of layer l are final:
@@ -23,23 +23,19 @@
 //   backward  BQ by query, L + 2 sweeps of one kernel: sweep s = 0 .. L stops at layer lo = L - s and takes sum dz_lo, sum dz_lo xh_lo (= d beta, d gamma),
 //             the last one forms dy_0: grad_center, partial sums of grad_w_pos.  A sweep that has dy_l adds h_{l-1}^T dy_l (MFMA, the pairs are the
 //             contraction) to the workgroup's fp32 partial of grad_hidden_w.  'max': the first sweep counts the ties against the forward's `out`.
-//             bn_mode 0 / 2: one sweep.  BT by target over the transposed table: chunks of R pairs walk forward and back to dy_0 with every sum final;
-//             a target whose pairs span several chunks is continued by the same thread of the same workgroup.
+//             bn_mode 0 / 2: one sweep.  BT by target over the transposed table: chunks of R pairs walk forward and back to dy_0 with every sum final.
 // No float atomics; every output is stored once in a fixed order.  LDS: one of three static sizes (32 / 64 / 120 KB of rows + 21 KB of row data, layer
 // constants and the reduction scratch) of gfx950's 160 KB.
-#include "cbl_common.h"
+#include "pair_tile.h"
 
 namespace {
 
-using plm_f32x4 = __attribute__((ext_vector_type(4))) float;
-
 enum { PLM_BN_NONE = 0, PLM_BN_BATCH = 1, PLM_BN_MOVING = 2 };
-enum { PLM_SUM = 0, PLM_MEAN = 1, PLM_MAX = 2 };
-constexpr int PLM_BLOCK = 256, PLM_WAVES = 4, PLM_RMAX = 256, PLM_NCT = 9, PLM_YCT = 4, PLM_LAYW = 160;
+constexpr int PLM_YCT = 4, PLM_LAYW = 160;
 constexpr int PLM_HMIN = 16, PLM_HMAX = 144, PLM_KMAX = 128, PLM_KWIDE = 48, PLM_HNARROW = 64, PLM_CMAX = 1024;
 // grid caps (two workgroups per compute unit; a trip is a chain of phases behind barriers); BQ's also bounds the fp32 weight partials: at most
-// PLM_BQ_PARTIAL floats of them, never fewer than PLM_BQ_BLOCKS_MIN workgroups; the most targets of a BT trip
-constexpr int PLM_F_BLOCKS = 512, PLM_BQ_BLOCKS = 512, PLM_BQ_BLOCKS_MIN = 64, PLM_BQ_PARTIAL = 1 << 24, PLM_BT_BLOCKS = 512, PLM_TPT_MAX = 16;
+// PAIR_BQ_PARTIAL floats of them, never fewer than PLM_BQ_BLOCKS_MIN workgroups
+constexpr int PLM_F_BLOCKS = 512, PLM_BQ_BLOCKS = 512, PLM_BQ_BLOCKS_MIN = 64, PLM_BT_BLOCKS = 512;
 constexpr int PLM_LDS0 = 8192, PLM_LDS1 = 16384, PLM_LDS2 = 30720;                                 // floats of row buffers
 
 struct PlmArgs {
@@ -63,20 +59,17 @@ struct PlmLds { float* buf; float* dp; int* rowI; int* rowJ; int* rowC; float* c
 struct PlmCol { float mu, is, ga, be, k0, k1; };
 
 #define PLM_LDS_DECL(L)                                                                                                                  \
-    __shared__ float plm_buf[LDSF]; __shared__ float plm_dp[PLM_RMAX * 3]; __shared__ int plm_ri[PLM_RMAX]; __shared__ int plm_rj[PLM_RMAX];   \
-    __shared__ int plm_rc[PLM_RMAX]; __shared__ float plm_cnt[PLM_RMAX]; __shared__ float plm_lay[2 * 6 * PLM_LAYW];                    \
-    __shared__ double plm_red[3 * PLM_BLOCK];                                                                                           \
+    __shared__ float plm_buf[LDSF]; __shared__ float plm_dp[PAIR_RMAX * 3]; __shared__ int plm_ri[PAIR_RMAX]; __shared__ int plm_rj[PAIR_RMAX];   \
+    __shared__ int plm_rc[PAIR_RMAX]; __shared__ float plm_cnt[PAIR_RMAX]; __shared__ float plm_lay[2 * 6 * PLM_LAYW];                    \
+    __shared__ double plm_red[3 * PAIR_BLOCK];                                                                                           \
     PlmLds L; L.buf = plm_buf; L.dp = plm_dp; L.rowI = plm_ri; L.rowJ = plm_rj; L.rowC = plm_rc; L.cnt = plm_cnt; L.lay = plm_lay; L.red = plm_red
 
-__device__ __forceinline__ bool plm_real(int id, int n0) { return id >= 0 && id < n0; }
-__device__ __forceinline__ float plm_act(int act, float z) { return act == 1 ? (z > 0.f ? z : 0.f) : act == 2 ? (z > 0.f ? z : 0.2f * z) : z; }
-__device__ __forceinline__ float plm_dact(int act, float z) { return act == 1 ? (z > 0.f ? 1.f : 0.f) : act == 2 ? (z > 0.f ? 1.f : 0.2f) : 1.f; }
 // the constants of hidden layer l at column k: 0 mean, 1 invstd, 2 gamma, 3 beta, 4 sum dz / N, 5 sum dz xh / N — all zero in the padded columns
 __device__ __forceinline__ float plm_lay(const PlmLds& L, int l, int which, int k) { return L.lay[(l * 6 + which) * PLM_LAYW + k]; }
 // h_l from the stored xh_l (exactly 0 in a padded column: gamma = beta = 0 there)
 __device__ __forceinline__ float plm_h(const PlmArgs& a, const PlmLds& L, int l, float xh, int k)
 {
-    return plm_act(a.act, plm_lay(L, l, 2, k) * xh + plm_lay(L, l, 3, k));
+    return pair_act(a.act, plm_lay(L, l, 2, k) * xh + plm_lay(L, l, 3, k));
 }
 // gradient at y through the batch norm from the gradient at z
 __device__ __forceinline__ float plm_bn_back(int bn, float ga, float is, float k0, float k1, float dz, float xh)
@@ -88,7 +81,7 @@ __device__ __forceinline__ float plm_bn_back(int bn, float ga, float is, float k
 
 __device__ __forceinline__ void plm_load_layers(const PlmArgs& a, const PlmLds& L, const float* coef)
 {
-    for (int it = threadIdx.x; it < 2 * PLM_LAYW; it += PLM_BLOCK) {
+    for (int it = threadIdx.x; it < 2 * PLM_LAYW; it += PAIR_BLOCK) {
         const int l = it / PLM_LAYW, k = it - l * PLM_LAYW;
         const bool live = l < a.L && k < a.H, bn = a.bn != PLM_BN_NONE;
         const int at = l * a.H + k;
@@ -117,92 +110,18 @@ __device__ __forceinline__ PlmCol plm_col(const PlmArgs& a, const float* coef, i
     return t;
 }
 
-// the rows of a query trip: row r = (query i0 + r / K, neighbour r % K); rowI -1 on a row past the trip's pairs, rowJ the neighbour id (shadow: >= n0),
-// rowC the id of the query's centre row idx[i, 0]; dp (:563-564, the shadow point is the origin); cnt[qi] = the count behind 'mean' (:609-613)
-__device__ __forceinline__ void plm_rows_query(const PlmArgs& a, const PlmLds& L, int i0, int pad)
-{
-    for (int r = threadIdx.x; r < a.R; r += PLM_BLOCK) {
-        const int qi = r / a.K, k = r - qi * a.K, i = i0 + qi;
-        const bool valid = qi < a.tq && i < a.n;
-        int id = -1;
-        float d0 = 0.f, d1 = 0.f, d2 = 0.f;
-        if (valid) {
-            id = a.idx[(size_t)i * a.K + k];
-            float sx = 0.f, sy = 0.f, sz = 0.f;
-            if (plm_real(id, a.n0)) { sx = a.s[3 * (size_t)id]; sy = a.s[3 * (size_t)id + 1]; sz = a.s[3 * (size_t)id + 2]; }
-            d0 = (sx - a.q[3 * (size_t)i]) * a.inv_radius; d1 = (sy - a.q[3 * (size_t)i + 1]) * a.inv_radius; d2 = (sz - a.q[3 * (size_t)i + 2]) * a.inv_radius;
-        }
-        L.rowI[r] = valid ? i : -1; L.rowJ[r] = id; L.rowC[r] = valid ? a.idx[(size_t)i * a.K] : -1;
-        L.dp[3 * r] = d0; L.dp[3 * r + 1] = d1; L.dp[3 * r + 2] = d2;
-    }
-    for (int qi = threadIdx.x; qi < a.tq; qi += PLM_BLOCK) {
-        const int i = i0 + qi;
-        int cnt = 0;
-        if (i < a.n && a.red == PLM_MEAN)
-            for (int k = 0; k < a.K; k++) cnt += (a.idx[(size_t)i * a.K + k] < pad) ? 1 : 0;
-        L.cnt[qi] = (float)cnt;
-    }
-}
-
-// fc_0: X[r][m] = xh_0 (raw: y_0 itself, for the statistics sweep), zero on the padding rows and columns — ONE expression for every pass
+// fc_0: X[r][m] = xh_0 (raw: y_0 itself, for the statistics sweep)
 __device__ __forceinline__ void plm_first(const PlmArgs& a, const PlmLds& L, float* __restrict__ X, bool raw)
 {
-#pragma unroll 4
-    for (int it = threadIdx.x; it < a.R * a.HP; it += PLM_BLOCK) {
-        const int r = it / a.HP, m = it - r * a.HP, i = L.rowI[r];
-        float v = 0.f;
-        if (i >= 0 && m < a.H) {
-            const int id = L.rowJ[r], c0 = L.rowC[r];
-            const float w0 = a.wp ? a.wp[m] : 0.f, w1 = a.wp ? a.wp[a.H + m] : 0.f, w2 = a.wp ? a.wp[2 * a.H + m] : 0.f;
-            const float ce = (a.cen && plm_real(c0, a.n0)) ? a.cen[(size_t)c0 * a.H + m] : 0.f;
-            const float nb = (a.nbr && plm_real(id, a.n0)) ? a.nbr[(size_t)id * a.H + m] : 0.f;
-            const float y0 = (((L.dp[3 * r] * w0 + L.dp[3 * r + 1] * w1) + L.dp[3 * r + 2] * w2) + ce) + nb;
-            v = raw ? y0 : (y0 - plm_lay(L, 0, 0, m)) * plm_lay(L, 0, 1, m);
-        }
-        X[r * a.LDH + m] = v;
-    }
-}
-
-// A product on MFMA, a wave per 16-row tile with every column tile's accumulator in registers: acc(row, col) = init(row, col) + sum_k fa(row, k) fb(k, col),
-// k < KP (a multiple of 4), handed to fe(row, col, value).  A[i][k] in lane i + 16 k, B[k][j] in lane 16 k + j, D[4 (lane / 16) + v][lane % 16] in element v.
-// A wave reads all of its tile's operands before fe runs, and the tiles of different waves are different rows: fe may overwrite what fa read.
-template <int NCT, class FA, class FB, class FI, class FE>
-__device__ __forceinline__ void plm_mfma(int R, int KP, int nct, FA fa, FB fb, FI fi, FE fe)
-{
-    const int wave = threadIdx.x / CBL_WAVE, lane = threadIdx.x % CBL_WAVE, li = lane % 16, lk = lane / 16;
-    for (int t = wave; t < R / 16; t += PLM_WAVES) {
-        plm_f32x4 acc[NCT];
-#pragma unroll
-        for (int c = 0; c < NCT; c++) {
-            acc[c] = plm_f32x4{0.f, 0.f, 0.f, 0.f};
-            if (c >= nct) continue;
-#pragma unroll
-            for (int v = 0; v < 4; v++) acc[c][v] = fi(16 * t + 4 * lk + v, 16 * c + li);
-        }
-#pragma unroll 4
-        for (int k0 = 0; k0 < KP; k0 += 4) {
-            const int kk = k0 + lk;
-            const float av = fa(16 * t + li, kk);
-#pragma unroll
-            for (int c = 0; c < NCT; c++) {
-                if (c >= nct) continue;
-                acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, fb(kk, 16 * c + li), acc[c], 0, 0, 0);
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < NCT; c++) {
-            if (c >= nct) continue;
-#pragma unroll
-            for (int v = 0; v < 4; v++) fe(16 * t + 4 * lk + v, 16 * c + li, acc[c][v]);
-        }
-    }
+    pair_fold_rows(a, L, a.H, a.HP, a.wp, a.cen, a.nbr, X, a.LDH,
+                   [&](int m, float y0) { return raw ? y0 : (y0 - plm_lay(L, 0, 0, m)) * plm_lay(L, 0, 1, m); });
 }
 
 // fc_1 of fc_num 3: X1 = xh_1 (raw: y_1) from xh_0
 __device__ __forceinline__ void plm_hidden(const PlmArgs& a, const PlmLds& L, const float* X0, float* X1, bool raw)
 {
     const float* __restrict__ W = a.hw;
-    plm_mfma<PLM_NCT>(a.R, a.HP, a.nct,
+    pair_mfma<PAIR_NCT>(a.R, a.HP, a.nct,
         [&](int r, int k) { return plm_h(a, L, 0, X0[r * a.LDH + k], k); },
         [&](int k, int c) { return (k < a.H && c < a.H) ? W[(size_t)k * a.H + c] : 0.f; },
         [&](int, int) { return 0.f; },
@@ -213,7 +132,7 @@ __device__ __forceinline__ void plm_last(const PlmArgs& a, const PlmLds& L, cons
 {
     const float* __restrict__ W = a.hw + (a.L == 2 ? (size_t)a.H * a.H : 0);
     const int l = a.L - 1;
-    plm_mfma<PLM_YCT>(a.R, a.HP, a.CT / 16,
+    pair_mfma<PLM_YCT>(a.R, a.HP, a.CT / 16,
         [&](int r, int k) { return plm_h(a, L, l, X[r * a.LDH + k], k); },
         [&](int k, int c) { return (k < a.H && c0 + c < a.C) ? W[(size_t)k * a.C + c0 + c] : 0.f; },
         [&](int, int) { return 0.f; },
@@ -225,7 +144,7 @@ __device__ __forceinline__ void plm_last(const PlmArgs& a, const PlmLds& L, cons
 template <int V, class F>
 __device__ __forceinline__ void plm_colsum(const PlmLds& L, int R, int width, bool first, double* __restrict__ dst, size_t stride, F f)
 {
-    const int nsl = PLM_BLOCK / width, sl = threadIdx.x / width, c = threadIdx.x - sl * width;
+    const int nsl = PAIR_BLOCK / width, sl = threadIdx.x / width, c = threadIdx.x - sl * width;
     if (sl < nsl) {
         double s[V];
 #pragma unroll
@@ -238,14 +157,14 @@ __device__ __forceinline__ void plm_colsum(const PlmLds& L, int R, int width, bo
             for (int v = 0; v < V; v++) s[v] += t[v];
         }
 #pragma unroll
-        for (int v = 0; v < V; v++) L.red[v * PLM_BLOCK + threadIdx.x] = s[v];
+        for (int v = 0; v < V; v++) L.red[v * PAIR_BLOCK + threadIdx.x] = s[v];
     }
     __syncthreads();
     if (sl == 0) {
 #pragma unroll
         for (int v = 0; v < V; v++) {
             double t = 0.0;
-            for (int j = 0; j < nsl; j++) t += L.red[v * PLM_BLOCK + j * width + c];
+            for (int j = 0; j < nsl; j++) t += L.red[v * PAIR_BLOCK + j * width + c];
             double* d = dst + (size_t)v * stride + c;
             *d = first ? t : *d + t;
         }
@@ -253,39 +172,14 @@ __device__ __forceinline__ void plm_colsum(const PlmLds& L, int R, int width, bo
     __syncthreads();
 }
 
-// dst[p][col0 + c] (+)= sum_r h(r, p) D[r][c] for p < H, c < cw: tile (tp, tc) of wave (tp ntc + tc) % 4, continued from the workgroup's own fp32 partial
-template <class FH>
-__device__ __forceinline__ void plm_wgrad(const PlmArgs& a, FH h, const float* D, int ldd, int ntc, int cw, float* __restrict__ dst, int ldw, int col0, bool first)
-{
-    const int wave = threadIdx.x / CBL_WAVE, lane = threadIdx.x % CBL_WAVE, li = lane % 16, lk = lane / 16;
-    for (int tile = wave; tile < a.nct * ntc; tile += PLM_WAVES) {
-        const int tp = tile / ntc, tc = tile - tp * ntc, col = 16 * tc + li;
-        plm_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        if (!first) {
-#pragma unroll
-            for (int v = 0; v < 4; v++) {
-                const int p = 16 * tp + 4 * lk + v;
-                if (p < a.H && col < cw) acc[v] = dst[(size_t)p * ldw + col0 + col];
-            }
-        }
-        for (int r0 = 0; r0 < a.R; r0 += 4)
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(h(r0 + lk, 16 * tp + li), D[(r0 + lk) * ldd + col], acc, 0, 0, 0);
-#pragma unroll
-        for (int v = 0; v < 4; v++) {
-            const int p = 16 * tp + 4 * lk + v;
-            if (p < a.H && col < cw) dst[(size_t)p * ldw + col0 + col] = acc[v];
-        }
-    }
-}
-
 // ---------------------------------------------------------------- forward
 // upto = the layer whose sum y, sum y^2 this sweep takes (the layers below it have their statistics); upto = L + 1: normalise, activate, mask, reduce -> out.
 // partial: [WT sum y | WT sum y^2] per workgroup (PD doubles apart)
 template <int LDSF>
-__global__ __launch_bounds__(PLM_BLOCK) void plm_forward_kernel(PlmArgs a, int upto, double* __restrict__ partial, size_t PD, float* __restrict__ out)
+__global__ __launch_bounds__(PAIR_BLOCK) void plm_forward_kernel(PlmArgs a, int upto, double* __restrict__ partial, size_t PD, float* __restrict__ out)
 {
     PLM_LDS_DECL(L);
-    const int pad = (a.red == PLM_MEAN) ? *a.padding_num : 0;
+    const int pad = (a.red == PAIR_MEAN) ? *a.padding_num : 0;
     const int ntrips = (a.n + a.tq - 1) / a.tq;
     float* X0 = L.buf;
     float* X1 = L.buf + (size_t)a.R * a.LDH;
@@ -296,7 +190,7 @@ __global__ __launch_bounds__(PLM_BLOCK) void plm_forward_kernel(PlmArgs a, int u
     for (int trip = blockIdx.x; trip < ntrips; trip += gridDim.x) {
         const int i0 = trip * a.tq;
         const bool first = trip == (int)blockIdx.x;
-        plm_rows_query(a, L, i0, pad);
+        pair_rows_query(a, L, i0, pad);
         __syncthreads();
         plm_first(a, L, X0, upto == 0);
         __syncthreads();
@@ -322,18 +216,18 @@ __global__ __launch_bounds__(PLM_BLOCK) void plm_forward_kernel(PlmArgs a, int u
                 plm_colsum<2>(L, a.R, cw, first, mine + a.L * a.H + c0, (size_t)a.WT, [&](int r, int c, double (&t)[2]) { square(Y[r * a.LDY + c], t); });
                 continue;
             }
-            for (int it = threadIdx.x; it < a.tq * cw; it += PLM_BLOCK) {
+            for (int it = threadIdx.x; it < a.tq * cw; it += PAIR_BLOCK) {
                 const int qi = it / cw, c = it - qi * cw, i = i0 + qi;
                 if (i >= a.n) continue;
                 const PlmCol t = plm_col(a, nullptr, c0 + c);
-                float acc = a.red == PLM_MAX ? -INFINITY : 0.f;
+                float acc = a.red == PAIR_MAX ? -INFINITY : 0.f;
                 for (int k = 0; k < a.K; k++) {
                     const int r = qi * a.K + k;
                     const float xh = (Y[r * a.LDY + c] - t.mu) * t.is, z = t.ga * xh + t.be;
-                    const float av = plm_real(L.rowJ[r], a.n0) ? plm_act(a.act, z) : 0.f;          // activation * mask (:601): a shadow pair is 0, also under 'max'
-                    if (a.red == PLM_MAX) acc = av > acc ? av : acc; else acc += av;
+                    const float av = pair_real(L.rowJ[r], a.n0) ? pair_act(a.act, z) : 0.f;          // activation * mask (:601): a shadow pair is 0, also under 'max'
+                    if (a.red == PAIR_MAX) acc = av > acc ? av : acc; else acc += av;
                 }
-                if (a.red == PLM_MEAN) acc = acc / (L.cnt[qi] + 1e-5f);                              // :609-613
+                if (a.red == PAIR_MEAN) acc = acc / (L.cnt[qi] + 1e-5f);                              // :609-613
                 out[(size_t)i * a.C + c0 + c] = acc;
             }
             __syncthreads();
@@ -394,8 +288,8 @@ __device__ __forceinline__ void plm_walk(const PlmArgs& a, const PlmBwd& b, cons
         const int cw = min(a.CT, a.C - c0);
         plm_last(a, L, XL, Y, c0);
         __syncthreads();
-        if (em.ties && a.red == PLM_MAX) {                               // how many pairs attain each maximum (shadow pairs, value 0, count)
-            for (int it = threadIdx.x; it < a.tq * cw; it += PLM_BLOCK) {
+        if (em.ties && a.red == PAIR_MAX) {                               // how many pairs attain each maximum (shadow pairs, value 0, count)
+            for (int it = threadIdx.x; it < a.tq * cw; it += PAIR_BLOCK) {
                 const int qi = it / cw, c = it - qi * cw, i = i0 + qi;
                 if (i >= a.n) continue;
                 const PlmCol t = plm_col(a, nullptr, c0 + c);
@@ -404,7 +298,7 @@ __device__ __forceinline__ void plm_walk(const PlmArgs& a, const PlmBwd& b, cons
                 for (int k = 0; k < a.K; k++) {
                     const int r = qi * a.K + k;
                     const float xh = (Y[r * a.LDY + c] - t.mu) * t.is, z = t.ga * xh + t.be;
-                    tc += ((plm_real(L.rowJ[r], a.n0) ? plm_act(a.act, z) : 0.f) == m) ? 1.f : 0.f;
+                    tc += ((pair_real(L.rowJ[r], a.n0) ? pair_act(a.act, z) : 0.f) == m) ? 1.f : 0.f;
                 }
                 b.ties[(size_t)i * a.C + c0 + c] = tc;
             }
@@ -415,15 +309,15 @@ __device__ __forceinline__ void plm_walk(const PlmArgs& a, const PlmBwd& b, cons
             const int i = L.rowI[r];
             xh = (Y[r * a.LDY + c] - t.mu) * t.is;
             const float z = t.ga * xh + t.be;
-            if (i < 0 || !plm_real(L.rowJ[r], a.n0)) return 0.f;         // the mask sits behind the activation (:601): a shadow pair passes nothing on
+            if (i < 0 || !pair_real(L.rowJ[r], a.n0)) return 0.f;         // the mask sits behind the activation (:601): a shadow pair passes nothing on
             const size_t at = (size_t)i * a.C + c0 + c;
             const float g = b.go[at];
             float gf;
-            if (a.red == PLM_MAX) {
+            if (a.red == PAIR_MAX) {
                 const float tc = b.ties[at];
-                gf = (plm_act(a.act, z) == b.out[at] && tc > 0.f) ? g / tc : 0.f;
+                gf = (pair_act(a.act, z) == b.out[at] && tc > 0.f) ? g / tc : 0.f;
             } else gf = g * b.inv_nn[i];
-            return plm_dact(a.act, z) * gf;
+            return pair_dact(a.act, z) * gf;
         };
         if (sums(a.L)) {
             const PlmCol t = plm_col(a, nullptr, c0 + (int)threadIdx.x % cw);     // (plm_colsum's own column of this thread)
@@ -437,7 +331,7 @@ __device__ __forceinline__ void plm_walk(const PlmArgs& a, const PlmBwd& b, cons
         {                                                                // Y <- dy_L, zero on the padding rows and behind the last column (256 % CT == 0:
             const int c = threadIdx.x % a.CT;                            //  a thread keeps its column)
             const PlmCol t = plm_col(a, b.coef, c0 + c);
-            for (int r = threadIdx.x / a.CT; r < a.R; r += PLM_BLOCK / a.CT) {
+            for (int r = threadIdx.x / a.CT; r < a.R; r += PAIR_BLOCK / a.CT) {
                 float v = 0.f;
                 if (L.rowI[r] >= 0 && c < cw) {
                     float xh;
@@ -449,9 +343,10 @@ __device__ __forceinline__ void plm_walk(const PlmArgs& a, const PlmBwd& b, cons
         }
         __syncthreads();
         if (wgrad(a.L))
-            plm_wgrad(a, [&](int r, int p) { return plm_h(a, L, a.L - 1, XL[r * a.LDH + p], p); }, Y, a.LDY, a.CT / 16, cw, wsumL, a.C, c0, em.first);
+            pair_wgrad(a.R, a.nct, a.H, [&](int r, int p) { return plm_h(a, L, a.L - 1, XL[r * a.LDH + p], p); }, Y, a.LDY, a.CT / 16, cw, wsumL, a.C, c0,
+                       em.first);
         // dh_{L-1} (+)= dy_L @ W_L[:, c0 ..]^T
-        plm_mfma<PLM_NCT>(a.R, a.CT, a.nct,
+        pair_mfma<PAIR_NCT>(a.R, a.CT, a.nct,
             [&](int r, int k) { return Y[r * a.LDY + k]; },
             [&](int k, int c) { return (k < cw && c < a.H) ? WL[(size_t)c * a.C + c0 + k] : 0.f; },
             [&](int r, int c) { return c0 > 0 ? DH[r * a.LDH + c] : 0.f; },
@@ -464,7 +359,7 @@ __device__ __forceinline__ void plm_walk(const PlmArgs& a, const PlmBwd& b, cons
         // dz_l = dh_l act'(z_l): every valid row (a shadow pair is a pair like any other below the final mask)
         auto dzl = [&](int r, int m, float& xh) -> float {
             xh = X[r * a.LDH + m];
-            return DH[r * a.LDH + m] * plm_dact(a.act, plm_lay(L, l, 2, m) * xh + plm_lay(L, l, 3, m));
+            return DH[r * a.LDH + m] * pair_dact(a.act, plm_lay(L, l, 2, m) * xh + plm_lay(L, l, 3, m));
         };
         if (sums(l))
             plm_colsum<2>(L, a.R, a.H, em.first, em.sums + l * a.H, (size_t)a.WT, [&](int r, int m, double (&v)[2]) {
@@ -473,7 +368,7 @@ __device__ __forceinline__ void plm_walk(const PlmArgs& a, const PlmBwd& b, cons
                 v[0] = (double)dz; v[1] = (double)dz * (double)xh;
             });
         if (em.lo == l) return;
-        for (int it = threadIdx.x; it < a.R * a.HP; it += PLM_BLOCK) {   // dh_l -> dy_l in place
+        for (int it = threadIdx.x; it < a.R * a.HP; it += PAIR_BLOCK) {   // dh_l -> dy_l in place
             const int r = it / a.HP, m = it - r * a.HP;
             float v = 0.f;
             if (L.rowI[r] >= 0 && m < a.H) {
@@ -486,11 +381,12 @@ __device__ __forceinline__ void plm_walk(const PlmArgs& a, const PlmBwd& b, cons
         __syncthreads();
         if (l >= 1) {
             if (wgrad(l)) {
-                plm_wgrad(a, [&](int r, int p) { return plm_h(a, L, l - 1, X0[r * a.LDH + p], p); }, DH, a.LDH, a.nct, a.H, em.wsum, a.H, 0, em.first);
+                pair_wgrad(a.R, a.nct, a.H, [&](int r, int p) { return plm_h(a, L, l - 1, X0[r * a.LDH + p], p); }, DH, a.LDH, a.nct, a.H, em.wsum, a.H, 0,
+                           em.first);
                 __syncthreads();
             }
             const float* __restrict__ W = a.hw;                          // dh_{l-1} = dy_l @ W_l^T, in place
-            plm_mfma<PLM_NCT>(a.R, a.HP, a.nct,
+            pair_mfma<PAIR_NCT>(a.R, a.HP, a.nct,
                 [&](int r, int k) { return DH[r * a.LDH + k]; },
                 [&](int k, int c) { return (k < a.H && c < a.H) ? W[(size_t)c * a.H + k] : 0.f; },
                 [&](int, int) { return 0.f; },
@@ -503,11 +399,11 @@ __device__ __forceinline__ void plm_walk(const PlmArgs& a, const PlmBwd& b, cons
 
 // ---------------------------------------------------------------- BQ
 template <int LDSF>
-__global__ __launch_bounds__(PLM_BLOCK) void plm_bwd_query_kernel(PlmArgs a, PlmBwd b, int lo, int first_sweep, double* __restrict__ partial, size_t PD,
+__global__ __launch_bounds__(PAIR_BLOCK) void plm_bwd_query_kernel(PlmArgs a, PlmBwd b, int lo, int first_sweep, double* __restrict__ partial, size_t PD,
                                                                   float* __restrict__ wpartial, size_t PW, float* __restrict__ grad_center, int wpos)
 {
     PLM_LDS_DECL(L);
-    const int pad = (a.red == PLM_MEAN) ? *a.padding_num : 0;
+    const int pad = (a.red == PAIR_MEAN) ? *a.padding_num : 0;
     const int ntrips = (a.n + a.tq - 1) / a.tq;
     PlmEmit em;
     em.lo = lo; em.ties = first_sweep != 0;
@@ -517,15 +413,15 @@ __global__ __launch_bounds__(PLM_BLOCK) void plm_bwd_query_kernel(PlmArgs a, Plm
     for (int trip = blockIdx.x; trip < ntrips; trip += gridDim.x) {
         const int i0 = trip * a.tq;
         em.first = trip == (int)blockIdx.x;
-        plm_rows_query(a, L, i0, pad);
+        pair_rows_query(a, L, i0, pad);
         __syncthreads();
         if (first_sweep)
-            for (int qi = threadIdx.x; qi < a.tq; qi += PLM_BLOCK)
-                if (i0 + qi < a.n) b.inv_nn[i0 + qi] = a.red == PLM_MEAN ? 1.0f / (L.cnt[qi] + 1e-5f) : 1.0f;
+            for (int qi = threadIdx.x; qi < a.tq; qi += PAIR_BLOCK)
+                if (i0 + qi < a.n) b.inv_nn[i0 + qi] = a.red == PAIR_MEAN ? 1.0f / (L.cnt[qi] + 1e-5f) : 1.0f;
         __syncthreads();
         plm_walk(a, b, L, em, i0, [&](const float* DY) {
             if (grad_center) {
-                for (int it = threadIdx.x; it < a.tq * a.H; it += PLM_BLOCK) {
+                for (int it = threadIdx.x; it < a.tq * a.H; it += PAIR_BLOCK) {
                     const int qi = it / a.H, m = it - qi * a.H, i = i0 + qi;
                     if (i >= a.n) continue;
                     float s = 0.f;
@@ -579,7 +475,7 @@ __global__ __launch_bounds__(256) void plm_fin_w_kernel(int H, int WT, int nbloc
 
 // ---------------------------------------------------------------- BT
 template <int LDSF>
-__global__ __launch_bounds__(PLM_BLOCK) void plm_bwd_target_kernel(PlmArgs a, PlmBwd b, CblFastDiv dvK, const int* __restrict__ order,
+__global__ __launch_bounds__(PAIR_BLOCK) void plm_bwd_target_kernel(PlmArgs a, PlmBwd b, CblFastDiv dvK, const int* __restrict__ order,
                                                                    const int* __restrict__ inv_start, const int* __restrict__ inv_src,
                                                                    float* __restrict__ grad_neighbor)
 {
@@ -594,34 +490,10 @@ __global__ __launch_bounds__(PLM_BLOCK) void plm_bwd_target_kernel(PlmArgs a, Pl
         int ce = e_lo;
         do {                                                             // chunks of R pairs; at least one, so that a target without pairs is stored too
             const bool last = ce + a.R >= e_hi;
-            for (int r = threadIdx.x; r < a.R; r += PLM_BLOCK) {
-                const int e = ce + r;
-                int i = -1, j = -1;
-                float d0 = 0.f, d1 = 0.f, d2 = 0.f;
-                if (e < e_hi) {
-                    const int p = inv_src[e];
-                    i = (int)cbl_fastdiv((unsigned)p, dvK);
-                    j = a.idx[p];
-                    d0 = (a.s[3 * (size_t)j] - a.q[3 * (size_t)i]) * a.inv_radius; d1 = (a.s[3 * (size_t)j + 1] - a.q[3 * (size_t)i + 1]) * a.inv_radius;
-                    d2 = (a.s[3 * (size_t)j + 2] - a.q[3 * (size_t)i + 2]) * a.inv_radius;
-                }
-                L.rowI[r] = i; L.rowJ[r] = j; L.rowC[r] = i >= 0 ? a.idx[(size_t)i * a.K] : -1;
-                L.dp[3 * r] = d0; L.dp[3 * r + 1] = d1; L.dp[3 * r + 2] = d2;
-            }
+            pair_rows_target(a, L, dvK, inv_src, ce, e_hi);
             __syncthreads();
-            plm_walk(a, b, L, em, 0, [&](const float* DY) {
-                for (int it = threadIdx.x; it < a.tpt * a.H; it += PLM_BLOCK) {     // grad_neighbor[j, m] = sum over j's pairs of dy_0
-                    const int tl = it / a.H, m = it - tl * a.H, tr = t_lo + tl;
-                    if (tr >= t_hi) continue;
-                    const int s0 = inv_start[tr], s1 = inv_start[tr + 1];
-                    const bool begins = s0 >= ce && (s0 < ce + a.R || last);
-                    if (!begins && !(s0 < ce && s1 > ce)) continue;
-                    const int j = order ? order[tr] : tr;
-                    float s = 0.f;
-                    for (int e = max(s0, ce); e < min(s1, ce + a.R); e++) s += DY[(e - ce) * a.LDH + m];
-                    float* dst = grad_neighbor + (size_t)j * a.H + m;
-                    *dst = begins ? s : *dst + s;
-                }
+            plm_walk(a, b, L, em, 0, [&](const float* DY) {                     // grad_neighbor[j, m] = sum over j's pairs of dy_0
+                pair_target_sum(a, a.H, DY, a.LDH, t_lo, t_hi, ce, last, order, inv_start, grad_neighbor);
             });
             __syncthreads();
             ce += a.R;
@@ -633,52 +505,38 @@ __global__ __launch_bounds__(PLM_BLOCK) void plm_bwd_target_kernel(PlmArgs a, Pl
 int plm_check(int n, int n0, int K, int H, int C, int layers, float radius, int bn_mode, int activation, int reduction)
 {
     if (n < 0 || n0 < 0 || K <= 0 || H <= 0 || C <= 0 || layers < 0 || !(radius > 0.f)) return CBL_ERR_BAD_ARG;
-    if (bn_mode < 0 || bn_mode > PLM_BN_MOVING || activation < 0 || activation > 2 || reduction < 0 || reduction > PLM_MAX) return CBL_ERR_BAD_ARG;
+    if (bn_mode < 0 || bn_mode > PLM_BN_MOVING || activation < 0 || activation > 2 || reduction < 0 || reduction > PAIR_MAX) return CBL_ERR_BAD_ARG;
     if (layers < 1 || layers > 2 || K > PLM_KMAX || C % 4 != 0 || C > PLM_CMAX) return CBL_ERR_UNSUPPORTED;
     if (H < PLM_HMIN || H > PLM_HMAX || (K > PLM_KWIDE && H > PLM_HNARROW)) return CBL_ERR_UNSUPPORTED;
     return CBL_OK;
 }
 
-inline int plm_up16(int v) { return (v + 15) / 16 * 16; }
-// the LDS size (0, 1, 2), the row pitch, the last layer's tile width and the rows of a tile for `nbuf` R x LDH buffers + one R x (CT + 4): the smallest size
-// that holds `want` rows, else the smallest that holds `need`; rows HP + 4 floats apart and 64 columns where that fits, HP and 32 where not
-inline int plm_plan(PlmArgs& a, int nbuf, int need, int want, int* rows)
+// the plan of pair_plan_query / pair_plan_target — the LDS size (0, 1, 2), the row pitch, the last layer's tile width and the rows of a tile — for `nbuf`
+// R x LDH buffers + one R x (CT + 4): the smallest size that holds `want` rows, else the smallest that holds `need`; at each size rows HP + 4 floats apart
+// and 64 columns where that fits, HP and 32 where not.  The callable writes what it chose into a.nbuf, a.LDH, a.CT, a.LDY: use it within the expression
+// that makes it, on the args object that is launched
+inline auto plm_plan(PlmArgs& a, int nbuf)
 {
-    const int sizes[3] = {PLM_LDS0, PLM_LDS1, PLM_LDS2};
-    const int ct = a.C <= 16 ? 16 : a.C <= 32 ? 32 : 64;
-    a.nbuf = nbuf;
-    for (int pass = 0; pass < 2; pass++)
-        for (int z = 0; z < 3; z++)
-            for (int tight = 0; tight < 2; tight++) {
-                a.LDH = a.HP + (tight ? 0 : 4);
-                a.CT = (tight && ct > 32) ? 32 : ct;
-                a.LDY = a.CT + 4;
-                int r = sizes[z] / (nbuf * a.LDH + a.LDY) / 16 * 16;
-                if (r > PLM_RMAX) r = PLM_RMAX;
-                if (r >= (pass == 0 ? want : need)) { *rows = r; return z; }
-            }
-    *rows = 0;
-    return -1;
-}
-// a query pass: as many whole queries as the rows hold
-inline int plm_plan_query(PlmArgs& a, int nbuf)
-{
-    int rows;
-    const int z = plm_plan(a, nbuf, plm_up16(a.K), plm_up16(a.K) > 64 ? plm_up16(a.K) : 64, &rows);
-    if (z < 0) return z;
-    a.tq = rows / a.K;
-    if (a.n > 0 && a.tq > a.n) a.tq = a.n;
-    a.R = plm_up16(a.tq * a.K);
-    return z;
+    return [&a, nbuf](int need, int want, int* rows) {
+        const int sizes[3] = {PLM_LDS0, PLM_LDS1, PLM_LDS2};
+        const int ct = a.C <= 16 ? 16 : a.C <= 32 ? 32 : 64;
+        a.nbuf = nbuf;
+        for (int pass = 0; pass < 2; pass++)
+            for (int z = 0; z < 3; z++)
+                for (int tight = 0; tight < 2; tight++) {
+                    a.LDH = a.HP + (tight ? 0 : 4);
+                    a.CT = (tight && ct > 32) ? 32 : ct;
+                    a.LDY = a.CT + 4;
+                    const int r = pair_rows_fit(sizes[z], nbuf * a.LDH + a.LDY);
+                    if (r >= (pass == 0 ? want : need)) { *rows = r; return z; }
+                }
+        *rows = 0;
+        return -1;
+    };
 }
 
-inline size_t plm_up(size_t b) { return (b + 255) & ~(size_t)255; }
 inline size_t plm_pw(int H, int C, int layers) { return (layers == 2 ? (size_t)H * H : 0) + (size_t)H * C; }
-inline int plm_bq_blocks(size_t PW)
-{
-    const size_t fit = (size_t)PLM_BQ_PARTIAL / PW;
-    return fit > (size_t)PLM_BQ_BLOCKS ? PLM_BQ_BLOCKS : fit < (size_t)PLM_BQ_BLOCKS_MIN ? PLM_BQ_BLOCKS_MIN : (int)fit;
-}
+inline int plm_bq_blocks(size_t PW) { return pair_bq_blocks(PW, PLM_BQ_BLOCKS, PLM_BQ_BLOCKS_MIN); }
 struct PlmSpace { size_t partial, wpartial, coef, inv_nn, ties, total, PD, PW; };
 inline PlmSpace plm_space(int n, int H, int C, int layers)
 {
@@ -687,11 +545,11 @@ inline PlmSpace plm_space(int n, int H, int C, int layers)
     s.PD = 2 * WT + 3 * (size_t)H;
     s.PW = plm_pw(H, C, layers);
     s.partial = 0;
-    s.wpartial = plm_up(sizeof(double) * (size_t)(PLM_F_BLOCKS > PLM_BQ_BLOCKS ? PLM_F_BLOCKS : PLM_BQ_BLOCKS) * s.PD);
-    s.coef = s.wpartial + plm_up(sizeof(float) * (size_t)plm_bq_blocks(s.PW) * s.PW);
-    s.inv_nn = s.coef + plm_up(sizeof(float) * 2 * WT);
-    s.ties = s.inv_nn + plm_up(sizeof(float) * rows);
-    s.total = s.ties + plm_up(sizeof(float) * rows * C);
+    s.wpartial = pair_up256(sizeof(double) * (size_t)(PLM_F_BLOCKS > PLM_BQ_BLOCKS ? PLM_F_BLOCKS : PLM_BQ_BLOCKS) * s.PD);
+    s.coef = s.wpartial + pair_up256(sizeof(float) * (size_t)plm_bq_blocks(s.PW) * s.PW);
+    s.inv_nn = s.coef + pair_up256(sizeof(float) * 2 * WT);
+    s.ties = s.inv_nn + pair_up256(sizeof(float) * rows);
+    s.total = s.ties + pair_up256(sizeof(float) * rows * C);
     return s;
 }
 
@@ -700,7 +558,7 @@ inline PlmArgs plm_args(int n, int n0, int K, int H, int C, int layers, const fl
                         int act, int red, const int* padding_num)
 {
     PlmArgs a;
-    a.n = n; a.n0 = n0; a.K = K; a.H = H; a.HP = plm_up16(H); a.LDH = a.HP; a.nct = a.HP / 16; a.C = C; a.L = layers; a.WT = layers * H + C;
+    a.n = n; a.n0 = n0; a.K = K; a.H = H; a.HP = pair_up16(H); a.LDH = a.HP; a.nct = a.HP / 16; a.C = C; a.L = layers; a.WT = layers * H + C;
     a.act = act; a.bn = bn_mode; a.red = red; a.R = 16; a.tq = 1; a.tpt = 1; a.CT = 16; a.LDY = 20; a.nbuf = layers;
     a.q = q; a.s = s; a.idx = idx; a.cen = cen; a.nbr = nbr; a.wp = wp; a.hw = hw; a.gamma = gamma; a.beta = beta; a.mean = mean; a.invstd = invstd;
     a.inv_radius = 1.0f / radius; a.padding_num = padding_num;
@@ -709,12 +567,7 @@ inline PlmArgs plm_args(int n, int n0, int K, int H, int C, int layers, const fl
 
 }  // namespace
 
-#define PLM_LAUNCH(kernel, z, grid, st, ...)                                                                                         \
-    do {                                                                                                                             \
-        if ((z) == 0) hipLaunchKernelGGL(kernel<PLM_LDS0>, grid, dim3(PLM_BLOCK), 0, st, __VA_ARGS__);                               \
-        else if ((z) == 1) hipLaunchKernelGGL(kernel<PLM_LDS1>, grid, dim3(PLM_BLOCK), 0, st, __VA_ARGS__);                          \
-        else hipLaunchKernelGGL(kernel<PLM_LDS2>, grid, dim3(PLM_BLOCK), 0, st, __VA_ARGS__);                                        \
-    } while (0)
+#define PLM_LAUNCH(kernel, z, ...) PAIR_LAUNCH(kernel, z, PLM_LDS0, PLM_LDS1, PLM_LDS2, __VA_ARGS__)
 
 CBL_EXPORT size_t cbl_pointwise_mlp_layers_workspace_bytes(int n, int n0, int K, int H, int C_out, int layers)
 {
@@ -731,7 +584,7 @@ CBL_EXPORT int cbl_pointwise_mlp_layers_forward(int n, int n0, int K, int H, int
     const int rc = plm_check(n, n0, K, H, C_out, layers, radius, bn_mode, activation, reduction);
     if (rc) return rc;
     if (n == 0) return CBL_OK;
-    if (!query_points || !support_points || !neighbors_indices || !hidden_w || !out || (reduction == PLM_MEAN && !padding_num)) return CBL_ERR_BAD_ARG;
+    if (!query_points || !support_points || !neighbors_indices || !hidden_w || !out || (reduction == PAIR_MEAN && !padding_num)) return CBL_ERR_BAD_ARG;
     if (bn_mode != PLM_BN_NONE && (!save_mean || !save_invstd || !(eps > 0.f))) return CBL_ERR_BAD_ARG;
     if (bn_mode == PLM_BN_MOVING && (!moving_mean || !moving_var)) return CBL_ERR_BAD_ARG;
     if (bn_mode == PLM_BN_BATCH && (!workspace || !cbl_host_aligned16(workspace))) return CBL_ERR_BAD_ARG;
@@ -739,7 +592,7 @@ CBL_EXPORT int cbl_pointwise_mlp_layers_forward(int n, int n0, int K, int H, int
     hipStream_t st = cbl_stream(stream);
     PlmArgs a = plm_args(n, n0, K, H, C_out, layers, query_points, support_points, neighbors_indices, center_term, neighbor_term, w_pos, hidden_w, radius,
                          bn_mode, gamma, beta, save_mean, save_invstd, activation, reduction, padding_num);
-    const int z = plm_plan_query(a, layers);
+    const int z = pair_plan_query(a, plm_plan(a, layers));
     if (z < 0) return CBL_ERR_UNSUPPORTED;
     const PlmSpace sp = plm_space(n, H, C_out, layers);
     const unsigned g = cbl_grid_for(n, a.tq, PLM_F_BLOCKS);
@@ -771,8 +624,8 @@ CBL_EXPORT int cbl_pointwise_mlp_layers_backward_csr(int n, int n0, int K, int H
     const int rc = plm_check(n, n0, K, H, C_out, layers, radius, bn_mode, activation, reduction);
     if (rc) return rc;
     if (!grad_center && !grad_neighbor && !grad_w_pos && !grad_hidden_w && !grad_gamma && !grad_beta) return CBL_OK;
-    if (n > 0 && (!query_points || !support_points || !neighbors_indices || !hidden_w || !grad_out || (reduction == PLM_MEAN && !padding_num) ||
-                  (reduction == PLM_MAX && !out))) return CBL_ERR_BAD_ARG;
+    if (n > 0 && (!query_points || !support_points || !neighbors_indices || !hidden_w || !grad_out || (reduction == PAIR_MEAN && !padding_num) ||
+                  (reduction == PAIR_MAX && !out))) return CBL_ERR_BAD_ARG;
     if (bn_mode != PLM_BN_NONE && (!save_mean || !save_invstd)) return CBL_ERR_BAD_ARG;
     const bool table = grad_neighbor && n0 > 0;
     if (table && (!inv_start || !inv_src || !support_points)) return CBL_ERR_BAD_ARG;
@@ -799,7 +652,7 @@ CBL_EXPORT int cbl_pointwise_mlp_layers_backward_csr(int n, int n0, int K, int H
     PlmBwd b;
     b.go = grad_out; b.out = out; b.coef = coef;
     b.inv_nn = reinterpret_cast<float*>(base + sp.inv_nn); b.ties = reinterpret_cast<float*>(base + sp.ties);
-    const int zq = plm_plan_query(a, layers + 1);
+    const int zq = pair_plan_query(a, plm_plan(a, layers + 1));
     if (zq < 0) return CBL_ERR_UNSUPPORTED;
     const unsigned gq = cbl_grid_for(n, a.tq, plm_bq_blocks(sp.PW));
     const double N = (double)n * (double)K;
@@ -822,14 +675,8 @@ CBL_EXPORT int cbl_pointwise_mlp_layers_backward_csr(int n, int n0, int K, int H
         hipLaunchKernelGGL(plm_fin_w_kernel, dim3(cbl_grid_for((long long)(sp.PW + 3 * (size_t)H), 256, 1024)), dim3(256), 0, st, H, a.WT, (int)gq, sp.PW, sp.PD,
                            (const float*)wpartial, (const double*)partial, grad_hidden_w, grad_w_pos);
     if (table) {
-        // a trip's targets: about one tile of pairs at the table's mean segment length (the chunk loop takes whatever a trip really has)
-        int rows;
-        const int zt = plm_plan(a, layers + 1, 16, 128, &rows);
+        const int zt = pair_plan_target(a, plm_plan(a, layers + 1));
         if (zt < 0) return CBL_ERR_UNSUPPORTED;
-        a.R = rows;
-        const long long mean = ((long long)n * K + n0 - 1) / n0;
-        long long tpt = rows / (mean > 0 ? mean : 1);
-        a.tpt = (int)(tpt < 1 ? 1 : tpt > PLM_TPT_MAX ? PLM_TPT_MAX : tpt);
         a.tq = 0;
         PLM_LAUNCH(plm_bwd_target_kernel, zt, dim3(cbl_grid_for(n0, a.tpt, PLM_BT_BLOCKS)), st, a, b, cbl_fastdiv_make((unsigned)K), order_dst, inv_start,
                    inv_src, grad_neighbor);

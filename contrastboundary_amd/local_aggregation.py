@@ -96,9 +96,7 @@ class _AdaptiveWeight(Function):
         n, K = neighbors_indices.shape
         n0, C = features.shape
         L = _lib.lib()
-        pad = torch.empty(1, dtype=torch.int32, device=features.device)
-        if reduction_mean:
-            _lib.check(L.cbl_index_max(ctypes.c_longlong(n * K), _lib.ptr(neighbors_indices), _lib.ptr(pad), _lib.stream_of(features)), "cbl_index_max")
+        pad = _padding_num(neighbors_indices, reduction_mean, _lib.stream_of(features))
         out = torch.empty((n, C), dtype=torch.float32, device=features.device)
         from . import pointops
         order = pointops.spatial_order(query_points)             # processing order only: same values (None: the rows as they are)
@@ -151,6 +149,33 @@ _AW_REDUCTIONS = {"sum": 0, "mean": 1, "avg": 1, "max": 2}
 _NO_TABLE = "{}: no transposed neighbour table for more than 2^20 support points, and there is no scatter form"
 
 
+def _padding_num(idx, red_is_mean, stream):
+    """-> the one-int device tensor behind 'mean' (max(idx), :466-470): filled only when the reduction is 'mean'"""
+    pad = torch.empty(1, dtype=torch.int32, device=idx.device)
+    if red_is_mean:
+        _lib.check(_lib.lib().cbl_index_max(ctypes.c_longlong(idx.numel()), _lib.ptr(idx), _lib.ptr(pad), stream), "cbl_index_max")
+    return pad
+
+
+def _pair_table(idx, n0, op_name):
+    """-> (order, inv_start, inv_src) of the transposed neighbour table, built if need be; the operators without a scatter form refuse where there is none"""
+    from . import pointops
+    tr = pointops.neighbor_transpose(idx, n0, build=True)
+    if tr is None:
+        raise NotImplementedError(_NO_TABLE.format(op_name))
+    return tr
+
+
+def _center_rows_to_support(gc, idx, n0, width, op_name):
+    """per-query rows (n, width) onto the centre rows they came from (shadow_features[idx[:, 0]]) -> (n0, width): the row scatter as a gather over the table
+    of that one column"""
+    tr0 = _pair_table(idx[:, :1].contiguous(), n0, op_name)
+    gcen = torch.empty((n0, width), dtype=torch.float32, device=gc.device)
+    _lib.check(_lib.lib().cbl_grouping_backward_csr_rows(_i(n0), _i(width), _i(width), _i(0), _lib.ptr(gc), _lib.ptr(tr0[0]), _lib.ptr(tr0[1]), _lib.ptr(tr0[2]),
+                                                         _lib.ptr(gcen), _lib.stream_of(gc)), "cbl_grouping_backward_csr_rows")
+    return gcen
+
+
 def _aw_d_in(local_input_feature, in_fdim):
     blocks = local_input_feature.split("_")
     return 3 * ("dp" in blocks) + in_fdim * sum(b in blocks for b in ("fi", "df", "fj"))
@@ -183,9 +208,7 @@ class _AdaptiveWeightGeneral(Function):
         L = _lib.lib()
         dev = features.device
         st = _lib.stream_of(features)
-        pad = torch.empty(1, dtype=torch.int32, device=dev)
-        if red == 1:
-            _lib.check(L.cbl_index_max(ctypes.c_longlong(n * K), _lib.ptr(neighbors_indices), _lib.ptr(pad), st), "cbl_index_max")
+        pad = _padding_num(neighbors_indices, red == 1, st)
         out = torch.empty((n, C), dtype=torch.float32, device=dev)
         _lib.check(L.cbl_adaptive_weight_general_forward(_i(n), _i(n0), _i(K), _i(C), _i(M), _lib.ptr(query_points), _lib.ptr(support_points),
                                                          _lib.ptr(neighbors_indices), _lib.ptr(features), _lib.ptr(center_term), _lib.ptr(neighbor_term),
@@ -206,7 +229,6 @@ class _AdaptiveWeightGeneral(Function):
         L = _lib.lib()
         dev = f.device
         st = _lib.stream_of(f)
-        from . import pointops
         need = ctx.needs_input_grad
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
         gf = new(n0, C) if need[3] else None
@@ -216,25 +238,14 @@ class _AdaptiveWeightGeneral(Function):
         gb = new(M) if need[7] else None
         order = inv_start = inv_src = None
         if gf is not None or gn is not None:
-            tr = pointops.neighbor_transpose(idx, n0, build=True)
-            if tr is None:
-                raise NotImplementedError(_NO_TABLE.format("adaptive_weight"))
-            order, inv_start, inv_src = tr
+            order, inv_start, inv_src = _pair_table(idx, n0, "adaptive_weight")
         ws = torch.empty(max(L.cbl_adaptive_weight_general_workspace_bytes(_i(n), _i(n0), _i(K), _i(C), _i(M)), 1), dtype=torch.uint8, device=dev)
         _lib.check(L.cbl_adaptive_weight_general_backward_csr(_i(n), _i(n0), _i(K), _i(C), _i(M), _lib.ptr(q), _lib.ptr(s), _lib.ptr(idx), _lib.ptr(f),
                                                               _lib.ptr(cen), _lib.ptr(nbr), _lib.ptr(wp), _lib.ptr(bias), _f(radius), _i(softmax), _i(red),
                                                               _lib.ptr(pad), _lib.ptr(out), _lib.ptr(grad_out), _lib.ptr(order), _lib.ptr(inv_start),
                                                               _lib.ptr(inv_src), _lib.ptr(gf), _lib.ptr(gc), _lib.ptr(gn), _lib.ptr(gwp), _lib.ptr(gb),
                                                               _lib.ptr(ws), ctypes.c_size_t(ws.numel()), st), "cbl_adaptive_weight_general_backward_csr")
-        gcen = None
-        if gc is not None:
-            # per-query rows onto the centre rows they came from (shadow_features[idx[:, 0]]): the row scatter as a gather over the table of that one column
-            tr0 = pointops.neighbor_transpose(idx[:, :1].contiguous(), n0, build=True)
-            if tr0 is None:
-                raise NotImplementedError(_NO_TABLE.format("adaptive_weight"))
-            gcen = new(n0, M)
-            _lib.check(L.cbl_grouping_backward_csr_rows(_i(n0), _i(M), _i(M), _i(0), _lib.ptr(gc), _lib.ptr(tr0[0]), _lib.ptr(tr0[1]), _lib.ptr(tr0[2]),
-                                                        _lib.ptr(gcen), st), "cbl_grouping_backward_csr_rows")
+        gcen = _center_rows_to_support(gc, idx, n0, M, "adaptive_weight") if gc is not None else None
         return None, None, None, gf, gcen, gn, gwp, gb, None, None, None
 
 
@@ -251,9 +262,7 @@ class _AdaptiveWeightMLP(Function):
         L = _lib.lib()
         dev = features.device
         st = _lib.stream_of(features)
-        pad = torch.empty(1, dtype=torch.int32, device=dev)
-        if red == 1:
-            _lib.check(L.cbl_index_max(ctypes.c_longlong(n * K), _lib.ptr(neighbors_indices), _lib.ptr(pad), st), "cbl_index_max")
+        pad = _padding_num(neighbors_indices, red == 1, st)
         out = torch.empty((n, C), dtype=torch.float32, device=dev)
         _lib.check(L.cbl_adaptive_weight_mlp_forward(_i(n), _i(n0), _i(K), _i(C), _i(M), _lib.ptr(query_points), _lib.ptr(support_points),
                                                      _lib.ptr(neighbors_indices), _lib.ptr(features), _lib.ptr(center_term), _lib.ptr(neighbor_term),
@@ -275,7 +284,6 @@ class _AdaptiveWeightMLP(Function):
         L = _lib.lib()
         dev = f.device
         st = _lib.stream_of(f)
-        from . import pointops
         need = ctx.needs_input_grad
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
         gf = new(n0, C) if need[3] else None
@@ -287,10 +295,7 @@ class _AdaptiveWeightMLP(Function):
         ghb = new(layers, M) if need[9] else None
         order = inv_start = inv_src = None
         if gf is not None or gn is not None:
-            tr = pointops.neighbor_transpose(idx, n0, build=True)
-            if tr is None:
-                raise NotImplementedError(_NO_TABLE.format("adaptive_weight"))
-            order, inv_start, inv_src = tr
+            order, inv_start, inv_src = _pair_table(idx, n0, "adaptive_weight")
         ws = torch.empty(max(L.cbl_adaptive_weight_mlp_workspace_bytes(_i(n), _i(n0), _i(K), _i(C), _i(M), _i(layers)), 1), dtype=torch.uint8, device=dev)
         _lib.check(L.cbl_adaptive_weight_mlp_backward_csr(_i(n), _i(n0), _i(K), _i(C), _i(M), _lib.ptr(q), _lib.ptr(s), _lib.ptr(idx), _lib.ptr(f),
                                                           _lib.ptr(cen), _lib.ptr(nbr), _lib.ptr(wp), _lib.ptr(bias), _i(layers), _lib.ptr(hw), _lib.ptr(hb),
@@ -298,15 +303,7 @@ class _AdaptiveWeightMLP(Function):
                                                           _lib.ptr(order), _lib.ptr(inv_start), _lib.ptr(inv_src), _lib.ptr(gf), _lib.ptr(gc), _lib.ptr(gn),
                                                           _lib.ptr(gwp), _lib.ptr(gb), _lib.ptr(ghw), _lib.ptr(ghb), _lib.ptr(ws),
                                                           ctypes.c_size_t(ws.numel()), st), "cbl_adaptive_weight_mlp_backward_csr")
-        gcen = None
-        if gc is not None:
-            # per-query rows onto the centre rows they came from, as _AdaptiveWeightGeneral does
-            tr0 = pointops.neighbor_transpose(idx[:, :1].contiguous(), n0, build=True)
-            if tr0 is None:
-                raise NotImplementedError(_NO_TABLE.format("adaptive_weight"))
-            gcen = new(n0, M)
-            _lib.check(L.cbl_grouping_backward_csr_rows(_i(n0), _i(M), _i(M), _i(0), _lib.ptr(gc), _lib.ptr(tr0[0]), _lib.ptr(tr0[1]), _lib.ptr(tr0[2]),
-                                                        _lib.ptr(gcen), st), "cbl_grouping_backward_csr_rows")
+        gcen = _center_rows_to_support(gc, idx, n0, M, "adaptive_weight") if gc is not None else None
         return None, None, None, gf, gcen, gn, gwp, gb, ghw, ghb, None, None, None, None
 
 
@@ -443,9 +440,7 @@ class _PosPool(Function):
         n, K = neighbors_indices.shape
         n0, C = features.shape
         L = _lib.lib()
-        pad = torch.empty(1, dtype=torch.int32, device=features.device)
-        if red == 1:
-            _lib.check(L.cbl_index_max(ctypes.c_longlong(n * K), _lib.ptr(neighbors_indices), _lib.ptr(pad), _lib.stream_of(features)), "cbl_index_max")
+        pad = _padding_num(neighbors_indices, red == 1, _lib.stream_of(features))
         out = torch.empty((n, C), dtype=torch.float32, device=features.device)
         _lib.check(L.cbl_pospool_forward(_i(n), _i(n0), _i(K), _i(C), _lib.ptr(query_points), _lib.ptr(support_points), _lib.ptr(neighbors_indices),
                                          _lib.ptr(features), _f(radius), _i(pe), _i(red), _lib.ptr(pad), _lib.ptr(out), _lib.stream_of(features)),
@@ -512,9 +507,7 @@ class _PointWiseMLP(Function):
         L = _lib.lib()
         dev = neighbor_term.device
         st = _lib.stream_of(neighbor_term)
-        pad = torch.empty(1, dtype=torch.int32, device=dev)
-        if red == 1:
-            _lib.check(L.cbl_index_max(ctypes.c_longlong(n * K), _lib.ptr(neighbors_indices), _lib.ptr(pad), st), "cbl_index_max")
+        pad = _padding_num(neighbors_indices, red == 1, st)
         out = torch.empty((n, C), dtype=torch.float32, device=dev)
         save_mean = torch.empty(C, dtype=torch.float32, device=dev) if bn_mode else None
         save_invstd = torch.empty(C, dtype=torch.float32, device=dev) if bn_mode else None
@@ -538,7 +531,6 @@ class _PointWiseMLP(Function):
         L = _lib.lib()
         dev = nbr.device
         st = _lib.stream_of(nbr)
-        from . import pointops
         need = ctx.needs_input_grad
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
         gc = new(n, C) if cen is not None and need[3] else None
@@ -548,26 +540,14 @@ class _PointWiseMLP(Function):
         gb = new(C) if beta is not None and need[7] else None
         order = inv_start = inv_src = None
         if gn is not None:
-            tr = pointops.neighbor_transpose(idx, n0, build=True)
-            if tr is None:
-                raise NotImplementedError("pointwise_mlp: no transposed neighbour table for more than 2^20 support points, and there is no scatter form")
-            order, inv_start, inv_src = tr
+            order, inv_start, inv_src = _pair_table(idx, n0, "pointwise_mlp")
         ws = torch.empty(max(L.cbl_pointwise_mlp_workspace_bytes(_i(n), _i(n0), _i(K), _i(C)), 1), dtype=torch.uint8, device=dev)
         _lib.check(L.cbl_pointwise_mlp_backward_csr(_i(n), _i(n0), _i(K), _i(C), _lib.ptr(q), _lib.ptr(s), _lib.ptr(idx), _lib.ptr(cen), _lib.ptr(nbr),
                                                     _lib.ptr(wp), _f(radius), _i(bn_mode), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(save_mean),
                                                     _lib.ptr(save_invstd), _i(act), _i(red), _lib.ptr(pad), _lib.ptr(out), _lib.ptr(grad_out),
                                                     _lib.ptr(order), _lib.ptr(inv_start), _lib.ptr(inv_src), _lib.ptr(gc), _lib.ptr(gn), _lib.ptr(gwp),
                                                     _lib.ptr(gg), _lib.ptr(gb), _lib.ptr(ws), ctypes.c_size_t(ws.numel()), st), "cbl_pointwise_mlp_backward_csr")
-        gcen = None
-        if gc is not None:
-            # per-query rows onto the centre rows they came from (shadow_features[idx[:, 0]]): the row scatter as a gather over the table of that one column
-            idx0 = idx[:, :1].contiguous()
-            tr0 = pointops.neighbor_transpose(idx0, n0, build=True)
-            if tr0 is None:
-                raise NotImplementedError("pointwise_mlp: no transposed neighbour table for more than 2^20 support points, and there is no scatter form")
-            gcen = new(n0, C)
-            _lib.check(L.cbl_grouping_backward_csr_rows(_i(n0), _i(C), _i(C), _i(0), _lib.ptr(gc), _lib.ptr(tr0[0]), _lib.ptr(tr0[1]), _lib.ptr(tr0[2]),
-                                                        _lib.ptr(gcen), st), "cbl_grouping_backward_csr_rows")
+        gcen = _center_rows_to_support(gc, idx, n0, C, "pointwise_mlp") if gc is not None else None
         return (None, None, None, gcen, gn, gwp, gg, gb) + (None,) * 8
 
 
@@ -584,9 +564,7 @@ class _PointWiseMLPLayers(Function):
         L = _lib.lib()
         dev = neighbor_term.device
         st = _lib.stream_of(neighbor_term)
-        pad = torch.empty(1, dtype=torch.int32, device=dev)
-        if red == 1:
-            _lib.check(L.cbl_index_max(ctypes.c_longlong(n * K), _lib.ptr(neighbors_indices), _lib.ptr(pad), st), "cbl_index_max")
+        pad = _padding_num(neighbors_indices, red == 1, st)
         out = torch.empty((n, C_out), dtype=torch.float32, device=dev)
         WT = layers * H + C_out
         save_mean = torch.empty(WT, dtype=torch.float32, device=dev) if bn_mode else None
@@ -613,7 +591,6 @@ class _PointWiseMLPLayers(Function):
         L = _lib.lib()
         dev = nbr.device
         st = _lib.stream_of(nbr)
-        from . import pointops
         need = ctx.needs_input_grad
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
         WT = layers * H + C_out
@@ -625,10 +602,7 @@ class _PointWiseMLPLayers(Function):
         gb = new(WT) if beta is not None and need[8] else None
         order = inv_start = inv_src = None
         if gn is not None:
-            tr = pointops.neighbor_transpose(idx, n0, build=True)
-            if tr is None:
-                raise NotImplementedError("pointwise_mlp: no transposed neighbour table for more than 2^20 support points, and there is no scatter form")
-            order, inv_start, inv_src = tr
+            order, inv_start, inv_src = _pair_table(idx, n0, "pointwise_mlp")
         ws = torch.empty(max(L.cbl_pointwise_mlp_layers_workspace_bytes(_i(n), _i(n0), _i(K), _i(H), _i(C_out), _i(layers)), 1), dtype=torch.uint8, device=dev)
         _lib.check(L.cbl_pointwise_mlp_layers_backward_csr(_i(n), _i(n0), _i(K), _i(H), _i(C_out), _lib.ptr(q), _lib.ptr(s), _lib.ptr(idx), _lib.ptr(cen),
                                                            _lib.ptr(nbr), _lib.ptr(wp), _f(radius), _i(layers), _lib.ptr(hw), _i(bn_mode), _lib.ptr(gamma),
@@ -636,15 +610,7 @@ class _PointWiseMLPLayers(Function):
                                                            _lib.ptr(out), _lib.ptr(grad_out), _lib.ptr(order), _lib.ptr(inv_start), _lib.ptr(inv_src),
                                                            _lib.ptr(gc), _lib.ptr(gn), _lib.ptr(gwp), _lib.ptr(ghw), _lib.ptr(gg), _lib.ptr(gb), _lib.ptr(ws),
                                                            ctypes.c_size_t(ws.numel()), st), "cbl_pointwise_mlp_layers_backward_csr")
-        gcen = None
-        if gc is not None:
-            # per-query rows onto the centre rows they came from, as _PointWiseMLP does
-            tr0 = pointops.neighbor_transpose(idx[:, :1].contiguous(), n0, build=True)
-            if tr0 is None:
-                raise NotImplementedError("pointwise_mlp: no transposed neighbour table for more than 2^20 support points, and there is no scatter form")
-            gcen = new(n0, H)
-            _lib.check(L.cbl_grouping_backward_csr_rows(_i(n0), _i(H), _i(H), _i(0), _lib.ptr(gc), _lib.ptr(tr0[0]), _lib.ptr(tr0[1]), _lib.ptr(tr0[2]),
-                                                        _lib.ptr(gcen), st), "cbl_grouping_backward_csr_rows")
+        gcen = _center_rows_to_support(gc, idx, n0, H, "pointwise_mlp") if gc is not None else None
         return (None, None, None, gcen, gn, gwp, ghw, gg, gb) + (None,) * 10
 
 

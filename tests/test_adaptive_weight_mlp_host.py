@@ -28,12 +28,12 @@ SO = os.path.join(BUILD, "libadaptive_weight_mlp_host.so")
 ASAN_MAIN = os.path.join(HERE, "host_emul", "adaptive_weight_mlp_asan_main.cpp")
 ASAN_EXE = os.path.join(BUILD, "adaptive_weight_mlp_asan")
 SRCS = [os.path.join(CSRC, "adaptive_weight_mlp.hip")]
-DEPS = SRCS + [GEN, os.path.abspath(__file__), os.path.join(CSRC, "cbl_common.h"), os.path.join(ROOT, "include", "cbl_amd.h"),
+DEPS = SRCS + [GEN, os.path.abspath(__file__), os.path.join(CSRC, "cbl_common.h"), os.path.join(CSRC, "pair_tile.h"), os.path.join(ROOT, "include", "cbl_amd.h"),
                os.path.join(EMUL, "amdgcn.h"), os.path.join(EMUL, "hip", "hip_runtime.h")]
 INCLUDES = ["-I" + EMUL, "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
 cf = ctypes.c_float
 ACT = {"relu": 1, "leaky_relu": 2}
-# the grid caps and the most targets of a target-side trip (AWM_F_BLOCKS, AWM_BQ_BLOCKS, AWM_BT_BLOCKS, AWM_TPT_MAX of the kernel file)
+# the grid caps and the most targets of a target-side trip (AWM_F_BLOCKS, AWM_BQ_BLOCKS, AWM_BT_BLOCKS of the kernel file, PAIR_TPT_MAX of pair_tile.h)
 F_BLOCKS, BQ_BLOCKS, BT_BLOCKS, TPT_MAX = 1024, 1024, 1024, 16
 
 

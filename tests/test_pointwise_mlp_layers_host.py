@@ -27,7 +27,7 @@ SO = os.path.join(BUILD, "libpointwise_mlp_layers_host.so")
 ASAN_MAIN = os.path.join(HERE, "host_emul", "pointwise_mlp_layers_asan_main.cpp")
 ASAN_EXE = os.path.join(BUILD, "pointwise_mlp_layers_asan")
 SRCS = [os.path.join(CSRC, "pointwise_mlp_layers.hip")]
-DEPS = SRCS + [GEN, os.path.abspath(__file__), os.path.join(CSRC, "cbl_common.h"), os.path.join(ROOT, "include", "cbl_amd.h"),
+DEPS = SRCS + [GEN, os.path.abspath(__file__), os.path.join(CSRC, "cbl_common.h"), os.path.join(CSRC, "pair_tile.h"), os.path.join(ROOT, "include", "cbl_amd.h"),
                os.path.join(EMUL, "amdgcn.h"), os.path.join(EMUL, "hip", "hip_runtime.h")]
 INCLUDES = ["-I" + EMUL, "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
 cf = ctypes.c_float
