@@ -11,6 +11,8 @@ import ctypes
 import numpy as np
 import torch
 
+from tests.host_emul.host_build import size_t_results
+
 EPS, MOMENTUM = 1e-5, 0.1
 HUB, REPEATED = 2, 7                                                   # the unlisted target is n - 1, the repeated row n // 3
 COUNT0 = 3                                                             # num_batches_tracked before the forward pass
@@ -206,7 +208,7 @@ class Entries:
 
     def __init__(self, lib, backend):
         self.L, self.B = lib, backend
-        lib.cbl_attn_workspace_bytes.restype = ctypes.c_size_t
+        size_t_results(lib)
 
     def _call(self, name, *args):
         rc = getattr(self.L, name)(*args, self.B.stream)

@@ -18,6 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 from oracle import cbl_oracle as C                                    # noqa: E402
 from tests import oracle_lib as O                                     # noqa: E402
 from tests.host_emul import full_library                              # noqa: E402
+from tests.host_emul.host_build import P, size_t_results              # noqa: E402
 
 F = ctypes.c_float
 _L = None
@@ -26,15 +27,8 @@ _L = None
 def lib():
     global _L
     if _L is None:
-        _L = full_library.load()
-        for name in ("cbl_knnquery_workspace_bytes", "cbl_grid_subsampling_workspace_bytes", "cbl_radius_neighbors_workspace_bytes", "cbl_furthestsampling_workspace_bytes",
-                     "cbl_neighbor_transpose_workspace_bytes"):
-            getattr(_L, name).restype = ctypes.c_size_t
+        _L = size_t_results(full_library.load())
     return _L
-
-
-def P(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
 def aligned(shape, dtype=np.float32):
@@ -163,7 +157,7 @@ def subsample_case(rng, it):
 def pyramid_case(rng, it):
     """the ConvNet's input pyramid as one native call (cbl_pyramid, /root/reference/tensorflow/datasets/base.py:767-842) on drawn scenes — 1 .. 3 clouds, 1 .. 4 layers,
     neighbourhood limits 1 .. 40 — against the oracle's operators applied layer by layer, every table bit for bit"""
-    L = _full(["cbl_pyramid_layer_workspace_bytes"])
+    L = lib()
 
     def ptrs(arrs, count):
         a = (ctypes.c_void_p * count)()
@@ -330,13 +324,6 @@ def _held(fn, *args):
         return False
 
 
-def _full(names):
-    L = lib()
-    for name in names:
-        getattr(L, name).restype = ctypes.c_size_t
-    return L
-
-
 def gather_case(rng, it):
     """queryandgroup / grouping / interpolation / subtraction / aggregation (tests/test_pointops_gather_host.py's checks) over point counts, neighbour counts and
     channel counts on both sides of every kernel choice: one query point, K = 1, channel counts that are not a multiple of 4, rows that start on 4-byte boundaries"""
@@ -362,8 +349,7 @@ def aggregation_case(rng, it):
     """KPConv (MFMA and general kernels, scatter and gather backward), AdaptiveWeight, PosPool (tests/test_local_aggregation_host.py's checks): K = 1 .. 64 with
     shadow neighbours, widths 4 .. 288, 1 .. 16 kernel points"""
     import tests.test_local_aggregation_host as T
-    L = _full(["cbl_neighbor_transpose_workspace_bytes", "cbl_adaptive_weight_backward_csr_workspace_bytes", "cbl_kpconv_backward_csr_workspace_bytes",
-               "cbl_pospool_backward_csr_workspace_bytes"])
+    L = lib()
     which = int(rng.integers(0, 5))
     if which in (0, 2):
         K = int(rng.choice([1, 2, 3, 15, 16, 17, 31, 33, 48, 64])); C = int(rng.choice([4, 8, 12, 16, 20, 32, 64, 68, 72, 128] if which == 0 else [4, 8, 16, 32, 64, 72]))
@@ -382,7 +368,7 @@ def attention_case(rng, it):
     import tests.test_attention_host as A
     import tests.test_pt_layer_host as T
     import tests.test_pt_layer_wide_host as W
-    L = _full(["cbl_attn_workspace_bytes", "cbl_neighbor_transpose_workspace_bytes", "cbl_triple_linear_workspace_bytes", "cbl_pt_layer_workspace_bytes"])
+    L = lib()
     which = int(rng.integers(0, 5))
     n = int(rng.choice([9, 15, 16, 17, 63, 64, 65, 130, 400])); K = int(rng.choice([1, 2, 3, 8, 9, 16, 17, 32, 33, 64])); C = int(rng.choice([32, 64, 128, 256]))
     if which == 0:

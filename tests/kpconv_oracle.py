@@ -23,6 +23,7 @@ import functools
 import numpy as np
 
 from tests.attention_oracle import HostBackend  # noqa: F401  (the host buffers of the driver; the device file brings its own backend)
+from tests.host_emul.host_build import size_t_results
 
 EXTENT = 0.09375                                                       # 3 / 32: the same number in fp32 and float64
 OFFSET = (37.5, -12.25, 81.0)
@@ -287,7 +288,7 @@ class Entries:
 
     def __init__(self, lib, backend):
         self.L, self.B = lib, backend
-        lib.cbl_kpconv_backward_csr_workspace_bytes.restype = ctypes.c_size_t
+        size_t_results(lib)
 
     def _inputs(self, sc, keys, shift=0):
         return {k: self.B.put(getattr(sc, k), shift if k == "f" else 0) for k in keys}

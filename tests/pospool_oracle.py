@@ -31,6 +31,7 @@ import functools
 import numpy as np
 
 from tests.attention_oracle import HostBackend  # noqa: F401  (the host buffers of the driver; the device file brings its own backend)
+from tests.host_emul.host_build import size_t_results
 from tests.kpconv_oracle import OFFSET, bits, tables, transposed  # noqa: F401
 
 EMBEDDINGS = ("one", "xyz", "distance", "exp_-d", "direction_exp_-d", "direction_d", "sin_cos", "two_order", "three_order")     # include/cbl_amd.h
@@ -386,7 +387,7 @@ class Entries:
 
     def __init__(self, lib, backend):
         self.L, self.B = lib, backend
-        lib.cbl_pospool_backward_csr_workspace_bytes.restype = ctypes.c_size_t
+        size_t_results(lib)
 
     def _head(self, sc):
         return [_i(sc.n), _i(sc.n0), _i(sc.K), _i(sc.C)]

@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from tests.attention_oracle import close, small, neighbours, transposed
+from tests.host_emul.host_build import size_t_results
 
 PARAMS = ["Wp", "bp", "gamma_p", "beta_p", "W3C", "b3C", "gamma_c", "beta_c", "Wa", "ba", "gamma_g", "beta_g", "Wb", "bb"]
 FEATURES = ["x_q", "x_k", "x_v"]
@@ -231,9 +232,7 @@ class LayerEntries:
 
     def __init__(self, lib, backend):
         self.L, self.B = lib, backend
-        for name in ("cbl_pt_layer_workspace_bytes", "cbl_pt_layer_wide_workspace_bytes"):
-            if hasattr(lib, name):
-                getattr(lib, name).restype = ctypes.c_size_t
+        size_t_results(lib)
 
     def _arr3(self, bufs):
         return (ctypes.c_void_p * 3)(*[self.B.ptr(b).value for b in bufs])

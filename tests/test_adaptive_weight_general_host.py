@@ -5,67 +5,19 @@ fc_num 1: every local_input_feature, shared_channels, weight_softmax, sum / mean
 the chain back to the features and the weights are done here as the Python mirror does them (contrastboundary_amd/local_aggregation.adaptive_weight), in
 numpy.  Every 'max' gradient case asserts, from the oracle, that no arg-max flip between fp32 and float64 can occur (seeds chosen so)."""
 import ctypes
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import adaptive_weight_general_oracle as O
+from tests.host_emul.host_build import P, aligned, load, nans, transposed_table
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "contrastboundary_amd", "csrc")
-EMUL = os.path.join(HERE, "host_emul", "wave")
-GEN = os.path.join(HERE, "host_emul", "host_tu.py")
-TU = os.path.join(ROOT, "oracle", "_build", "adaptive_weight_general_host.cpp")
-SO = os.path.join(ROOT, "oracle", "_build", "libadaptive_weight_general_host.so")
 cf = ctypes.c_float
 
 
 @pytest.fixture(scope="module")
 def host():
-    srcs = [os.path.join(CSRC, "adaptive_weight_general.hip")]
-    deps = srcs + [GEN, os.path.abspath(__file__), os.path.join(CSRC, "cbl_common.h"), os.path.join(ROOT, "include", "cbl_amd.h"),
-                   os.path.join(EMUL, "amdgcn.h"), os.path.join(EMUL, "hip", "hip_runtime.h")]
-    os.makedirs(os.path.dirname(SO), exist_ok=True)
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call([sys.executable, GEN, TU] + srcs)
-        subprocess.check_call(["g++", "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                               "-I" + EMUL, "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, TU, "-o", SO])
-    L = ctypes.CDLL(SO)
-    L.cbl_adaptive_weight_general_workspace_bytes.restype = ctypes.c_size_t
-    return L
-
-
-def P(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
-
-
-def aligned(a):
-    """a copy of `a` whose data pointer is 16-byte aligned (rows are read as float4)"""
-    a = np.ascontiguousarray(a)
-    raw = np.zeros(a.nbytes + 16, np.uint8)
-    off = (-raw.ctypes.data) % 16
-    out = raw[off:off + a.nbytes].view(a.dtype).reshape(a.shape)
-    out[...] = a
-    return out
-
-
-def nans(*shape):
-    return aligned(np.full(shape, np.nan, np.float32))
-
-
-def transposed_table(idx, n0):
-    """cbl_neighbor_transpose's output, restated (as tests/test_local_aggregation_host.py)"""
-    flat = idx.reshape(-1)
-    keep = np.nonzero(flat < n0)[0]
-    order = np.argsort(flat[keep], kind="stable")
-    inv_src = keep[order].astype(np.int32)
-    inv_start = np.zeros(n0 + 1, np.int32)
-    np.add.at(inv_start, flat[keep] + 1, 1)
-    return np.cumsum(inv_start).astype(np.int32), inv_src
+    return load("adaptive_weight_general", ["adaptive_weight_general"])
 
 
 def run(L, case, softmax, reduction, backward=True):

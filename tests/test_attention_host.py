@@ -12,20 +12,14 @@ import pytest
 import torch
 
 from tests.host_emul import full_library
+from tests.host_emul.host_build import P, size_t_results
 
 F = ctypes.c_float
 
 
 @pytest.fixture(scope="module")
 def host():
-    L = full_library.load()
-    for name in ("cbl_attn_workspace_bytes", "cbl_neighbor_transpose_workspace_bytes", "cbl_triple_linear_workspace_bytes"):
-        getattr(L, name).restype = ctypes.c_size_t
-    return L
-
-
-def P(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+    return size_t_results(full_library.load())
 
 
 def close(got, ref, tol=2e-4):

@@ -4,39 +4,18 @@ neighbours, soft-nearest-neighbour or NCE loss, the gradient — /root/reference
 tests/golden/cbl_pytorch.npz): point mask bit for bit, loss and feature gradient within the kernels' 1e-4 contract.  Every lanes-per-row width of the kernel
 (d = 4 ... 64) and neighbour counts on both sides of a wave; the gradient through the scatter entry (no transposed table needed)."""
 import ctypes
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from oracle import cbl_oracle as C
 from tests import oracle_lib as O
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "contrastboundary_amd", "csrc")
-EMUL = os.path.join(HERE, "host_emul", "wave")
-GEN = os.path.join(HERE, "host_emul", "host_tu.py")
-TU = os.path.join(ROOT, "oracle", "_build", "cbl_host.cpp")
-SO = os.path.join(ROOT, "oracle", "_build", "libcbl_host.so")
+from tests.host_emul.host_build import P, load
 
 
 @pytest.fixture(scope="module")
 def host():
-    srcs = [os.path.join(CSRC, "cbl.hip"), os.path.join(CSRC, "cbl_pairs.hip")]
-    deps = srcs + [GEN, os.path.join(CSRC, "wave_ops.h"), os.path.join(CSRC, "cbl_common.h"), os.path.join(EMUL, "amdgcn.h"), os.path.join(EMUL, "hip", "hip_runtime.h")]
-    os.makedirs(os.path.dirname(SO), exist_ok=True)
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call([sys.executable, GEN, TU] + srcs)
-        subprocess.check_call(["g++", "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                               "-I" + EMUL, "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, TU, "-o", SO])
-    return ctypes.CDLL(SO)
-
-
-def P(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+    return load("cbl", ["cbl", "cbl_pairs"])
 
 
 def aligned(shape, dtype=np.float32):

@@ -5,9 +5,6 @@ for bit, loss and feature gradient within the kernels' 1e-4 contract.  Both flav
 sample roles and 'labelkl' soft labels), 'softnn' and 'nce', the 'S' margin, and both backward routes: the gather over the transposed neighbour table and
 the atomic scatter."""
 import ctypes
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -15,32 +12,15 @@ import torch
 
 from oracle import cbl_oracle as C
 from tests import oracle_lib as O
+from tests.host_emul.host_build import P
+from tests.test_cbl_host import host  # noqa: F401  (the fixture that builds and loads the host library)
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "contrastboundary_amd", "csrc")
-EMUL = os.path.join(HERE, "host_emul", "wave")
-GEN = os.path.join(HERE, "host_emul", "host_tu.py")
 F = ctypes.c_float
 
 WIDTHS = [1, 3, 12, 13, 20, 48, 68, 72, 96, 128, 200, 256, 512, 2304]
 NSAMPLES = [2, 17, 25, 36, 65]
 # every width with two neighbour counts, every neighbour count with several widths
 GRID = [(d, NSAMPLES[(k + s) % len(NSAMPLES)]) for k, d in enumerate(WIDTHS) for s in (1, 3)]
-
-
-@pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    out = tmp_path_factory.mktemp("cbl_wide_host")
-    tu, so = str(out / "cbl_wide_host.cpp"), str(out / "libcbl_wide_host.so")
-    subprocess.check_call([sys.executable, GEN, tu, os.path.join(CSRC, "cbl.hip"), os.path.join(CSRC, "cbl_pairs.hip")])
-    subprocess.check_call(["g++", "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                           "-I" + EMUL, "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, tu, "-o", so])
-    return ctypes.CDLL(so)
-
-
-def P(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
 def placed(shape, misalign=0, dtype=np.float32):

@@ -3,48 +3,20 @@ dispatch to the bucketed kernel of fps_bucket.hip above 3072 points, and the cha
 40960 -> 10240 -> 2560 -> 640 -> 160, /root/reference/pytorch/model/blocks.py:61-68) compiled for the HOST and run with wave semantics (tests/host_emul/wave),
 against the oracle's restatement of furthestsampling_cuda_kernel (sampling_cuda_kernel.cu:14-129): sample sequences bit for bit, stage by stage of a chain."""
 import ctypes
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import oracle_lib as O
+from tests.host_emul.host_build import P, load
 from tests.test_fps_bucket_host import cloud
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "contrastboundary_amd", "csrc")
-EMUL = os.path.join(HERE, "host_emul", "wave")
-GEN = os.path.join(HERE, "host_emul", "host_tu.py")
-BUILD = os.path.join(ROOT, "oracle", "_build")
-SO = os.path.join(BUILD, "libfps_host.so")
 FILES = ["fps", "fps_bucket", "knn_grid", "knn_exact", "knn_select", "knn_dispatch"]       # fps_bucket's bounding boxes come from knn_grid.hip
 
 
 @pytest.fixture(scope="module")
 def host():
-    srcs = [os.path.join(CSRC, f + ".hip") for f in FILES]
-    deps = srcs + [GEN, os.path.abspath(__file__), os.path.join(CSRC, "fps_wave.h"), os.path.join(CSRC, "cbl_common.h"), os.path.join(EMUL, "amdgcn.h"),
-                   os.path.join(EMUL, "hip", "hip_runtime.h"), os.path.join(EMUL, "rocprim", "device", "device_radix_sort.hpp")]
-    os.makedirs(BUILD, exist_ok=True)
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-        objs = []
-        for f, src in zip(FILES, srcs):
-            tu, obj = os.path.join(BUILD, f + "_host.cpp"), os.path.join(BUILD, f + "_fpshost.o")
-            subprocess.check_call([sys.executable, GEN, tu, src])
-            subprocess.check_call(["g++", "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-c", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                                   "-I" + EMUL, "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, tu, "-o", obj])
-            objs.append(obj)
-        subprocess.check_call(["g++", "-shared"] + objs + ["-o", SO])
-    L = ctypes.CDLL(SO)
-    L.cbl_furthestsampling_workspace_bytes.restype = ctypes.c_size_t
-    return L
-
-
-def P(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+    return load("fps", FILES)
 
 
 def sample(L, xyz, off, noff, cert_in=None, want_cert=False):

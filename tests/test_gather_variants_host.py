@@ -15,20 +15,14 @@ import pytest
 from oracle import voxelize_oracle as V
 from tests import oracle_lib as O
 from tests.host_emul import full_library
+from tests.host_emul.host_build import P, size_t_results
 
 F = ctypes.c_float
 
 
 @pytest.fixture(scope="module")
 def host():
-    L = full_library.load()
-    for name in ("cbl_neighbor_transpose_workspace_bytes", "cbl_pospool_backward_csr_workspace_bytes", "cbl_voxelize_workspace_bytes"):
-        getattr(L, name).restype = ctypes.c_size_t
-    return L
-
-
-def P(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+    return size_t_results(full_library.load())
 
 
 def bits(a):
@@ -140,7 +134,6 @@ def test_scatter_adds_as_gathers_over_the_transposed_table(host, n, m, K, c):
 def test_two_tables_of_one_geometry_transposed_together(host, n, Ka, Kb):
     """cbl_neighbor_transpose_pair: the K = 8 / 16 table of a stage's blocks and the K = 36 table of its CBL head (blocks.py:34-35, heads.py:190-196) by the same four
     launches — byte for byte the outputs of two cbl_neighbor_transpose calls, with and without a processing order, shadow entries left out"""
-    host.cbl_neighbor_transpose_pair_workspace_bytes.restype = ctypes.c_size_t
     xyz, _, idx_a, rng = scene(n, n, Ka, seed=n)
     idx_b, _ = O.knnquery(Kb, xyz, xyz, np.int32([n]), np.int32([n]))
     idx_b = np.ascontiguousarray(idx_b, np.int32)

@@ -101,5 +101,4 @@ def test_random_cases_equal_the_oracles_on_the_device(dev, monkeypatch, which, s
     for mod in (Z, G, A):
         monkeypatch.setattr(mod, "P", wrap)
     monkeypatch.setattr(Z, "lib", lambda: dev)
-    monkeypatch.setattr(Z, "_full", lambda names: dev)
     assert Z.run(which, seed, cases) == 0

@@ -127,7 +127,6 @@ def test_two_tables_of_one_geometry_transposed_together(m, n, ka, kb, ordered):
     os_d = o_d if m == n else None
     outs = [torch.full((n + 1,), -7, dtype=torch.int32, device="cuda"), torch.full((m * ka,), -7, dtype=torch.int32, device="cuda"),
             torch.full((n + 1,), -7, dtype=torch.int32, device="cuda"), torch.full((m * kb,), -7, dtype=torch.int32, device="cuda")]
-    L.cbl_neighbor_transpose_pair_workspace_bytes.restype = ctypes.c_size_t
     need = L.cbl_neighbor_transpose_pair_workspace_bytes(_i(m), _i(n), _i(ka), _i(kb))
     ws = torch.empty(max(need, 1), dtype=torch.uint8, device="cuda")
     _lib.check(L.cbl_neighbor_transpose_pair(_i(m), _i(n), _i(ka), _lib.ptr(a_d), _i(kb), _lib.ptr(b_d), _lib.ptr(os_d), _lib.ptr(o_d), *[_lib.ptr(t) for t in outs],

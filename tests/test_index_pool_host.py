@@ -4,56 +4,17 @@ backward reads) and the product's own table (cbl_neighbor_transpose); ind_closes
 cbl_grouping_backward_csr_rows over the table of the first column.  Against the float64 torch composition of tests/index_pool_oracle.py (a restatement:
 TensorFlow is absent) within the 1e-4 contract; grad_x is pre-filled with NaN (every row must be written)."""
 import ctypes
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import index_pool_oracle as O
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "contrastboundary_amd", "csrc")
-EMUL = os.path.join(HERE, "host_emul", "wave")
-GEN = os.path.join(HERE, "host_emul", "host_tu.py")
-TU = os.path.join(ROOT, "oracle", "_build", "index_pool_host.cpp")
-SO = os.path.join(ROOT, "oracle", "_build", "libindex_pool_host.so")
+from tests.host_emul.host_build import P, aligned, load, nans
 
 
 @pytest.fixture(scope="module")
 def host():
-    srcs = [os.path.join(CSRC, f) for f in ("local_aggregation.hip", "index_pool.hip", "neighbor_transpose.hip")]
-    deps = srcs + [GEN, os.path.abspath(__file__), os.path.join(CSRC, "cbl_common.h"), os.path.join(CSRC, "k4_rows_pipe.h"), os.path.join(ROOT, "include", "cbl_amd.h"),
-                   os.path.join(EMUL, "gather_wave.h"), os.path.join(EMUL, "amdgcn.h"), os.path.join(EMUL, "hip", "hip_runtime.h")]
-    os.makedirs(os.path.dirname(SO), exist_ok=True)
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call([sys.executable, GEN, TU] + srcs)
-        subprocess.check_call(["g++", "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                               "-I" + EMUL, "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, TU, "-o", SO])
-    L = ctypes.CDLL(SO)
-    L.cbl_ind_max_pool_backward_workspace_bytes.restype = ctypes.c_size_t
-    L.cbl_neighbor_transpose_workspace_bytes.restype = ctypes.c_size_t
-    return L
-
-
-def P(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
-
-
-def aligned(a, off=0):
-    """a copy of `a` whose data pointer is 16-byte aligned (off = 4: deliberately not)"""
-    a = np.ascontiguousarray(a)
-    raw = np.zeros(a.nbytes + 32, np.uint8)
-    o = (-raw.ctypes.data) % 16 + off
-    out = raw[o:o + a.nbytes].view(a.dtype).reshape(a.shape)
-    out[...] = a
-    return out
-
-
-def nans(*shape):
-    return aligned(np.full(shape, np.nan, np.float32))
+    return load("index_pool", ["local_aggregation", "index_pool", "neighbor_transpose"])
 
 
 def table(L, inds, n1):

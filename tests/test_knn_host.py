@@ -6,46 +6,19 @@ clouds, lattices (every row tied: the replay), ragged batches, queries that are 
 query, select-then-sort; the nested K = 36 / 16 search the bench step runs; brute force)."""
 import ctypes
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import oracle_lib as O
+from tests.host_emul.host_build import P, load
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "contrastboundary_amd", "csrc")
-EMUL = os.path.join(HERE, "host_emul", "wave")
-GEN = os.path.join(HERE, "host_emul", "host_tu.py")
-BUILD = os.path.join(ROOT, "oracle", "_build")
-SO = os.path.join(BUILD, "libknn_host.so")
 FILES = ["knn_exact", "knn_select", "knn_grid", "knn_dispatch"]
 
 
 @pytest.fixture(scope="module")
 def host():
-    srcs = [os.path.join(CSRC, f + ".hip") for f in FILES]
-    deps = srcs + [GEN, os.path.abspath(__file__), os.path.join(CSRC, "cbl_common.h"), os.path.join(CSRC, "grid_core.h"), os.path.join(EMUL, "amdgcn.h"),
-                   os.path.join(EMUL, "hip", "hip_runtime.h")]
-    os.makedirs(BUILD, exist_ok=True)
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-        objs = []
-        for f, src in zip(FILES, srcs):                               # one translation unit per file, as in the product build (their anonymous namespaces overlap)
-            tu, obj = os.path.join(BUILD, f + "_host.cpp"), os.path.join(BUILD, f + "_host.o")
-            subprocess.check_call([sys.executable, GEN, tu, src])
-            subprocess.check_call(["g++", "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-c", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                                   "-I" + EMUL, "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, tu, "-o", obj])
-            objs.append(obj)
-        subprocess.check_call(["g++", "-shared"] + objs + ["-o", SO])
-    L = ctypes.CDLL(SO)
-    L.cbl_knnquery_workspace_bytes.restype = ctypes.c_size_t
-    return L
-
-
-def P(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+    return load("knn", FILES)
 
 
 def cloud(kind, n, seed):

@@ -14,19 +14,13 @@ import pytest
 
 from tests import oracle_lib as O
 from tests.host_emul import full_library
+from tests.host_emul.host_build import P, size_t_results
 from tests.test_knn_host import cloud
 
 
 @pytest.fixture(scope="module")
 def host():
-    L = full_library.load()
-    for name in ("cbl_knnquery_workspace_bytes", "cbl_knnquery_prefix_workspace_bytes"):
-        getattr(L, name).restype = ctypes.c_size_t
-    return L
-
-
-def P(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+    return size_t_results(full_library.load())
 
 
 def scene():

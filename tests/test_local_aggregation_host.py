@@ -4,51 +4,17 @@ v_permlane16/32_swap, shuffles as rendezvous of a wave's fibres), through their 
 (oracle/local_aggregation_oracle.py) within the 1e-4 contract: the C <= 64 MFMA kernel with one and with several chunks of 16 neighbours, the general kernel,
 'closest' and constant influence, shadow (padding) neighbours, the scatter-form backward passes."""
 import ctypes
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from oracle import local_aggregation_oracle as LA
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "contrastboundary_amd", "csrc")
-EMUL = os.path.join(HERE, "host_emul", "wave")
-GEN = os.path.join(HERE, "host_emul", "host_tu.py")
-TU = os.path.join(ROOT, "oracle", "_build", "local_aggregation_host.cpp")
-SO = os.path.join(ROOT, "oracle", "_build", "liblocal_aggregation_host.so")
+from tests.host_emul.host_build import P, aligned, load, transposed_table
 
 
 @pytest.fixture(scope="module")
 def host():
-    srcs = [os.path.join(CSRC, "local_aggregation.hip"), os.path.join(CSRC, "kpconv_backward.hip"), os.path.join(CSRC, "pospool.hip")]
-    deps = srcs + [GEN, os.path.abspath(__file__), os.path.join(CSRC, "cbl_common.h"), os.path.join(EMUL, "amdgcn.h"), os.path.join(EMUL, "hip", "hip_runtime.h")]
-    os.makedirs(os.path.dirname(SO), exist_ok=True)
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call([sys.executable, GEN, TU] + srcs)
-        subprocess.check_call(["g++", "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                               "-I" + EMUL, "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, TU, "-o", SO])
-    L = ctypes.CDLL(SO)
-    L.cbl_kpconv_backward_csr_workspace_bytes.restype = ctypes.c_size_t
-    L.cbl_adaptive_weight_backward_csr_workspace_bytes.restype = ctypes.c_size_t
-    return L
-
-
-def P(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
-
-
-def aligned(a):
-    """a copy of `a` whose data pointer is 16-byte aligned (feature rows are read as float4)"""
-    a = np.ascontiguousarray(a)
-    raw = np.zeros(a.nbytes + 16, np.uint8)
-    off = (-raw.ctypes.data) % 16
-    out = raw[off:off + a.nbytes].view(a.dtype).reshape(a.shape)
-    out[...] = a
-    return out
+    return load("local_aggregation", ["local_aggregation", "kpconv_backward", "pospool"])
 
 
 def make(n0, n, K, C, seed, pad_frac=0.2):
@@ -104,18 +70,6 @@ def test_adaptive_weight_forward_and_backward(host, K, C, reduction):
     np.testing.assert_allclose(gf, rgf, rtol=1e-4, atol=1e-4 * np.abs(rgf).max())
     np.testing.assert_allclose(gW, rgW, rtol=1e-4, atol=1e-4 * np.abs(rgW).max())
     np.testing.assert_allclose(gb, rgb, rtol=1e-4, atol=1e-4 * np.abs(rgb).max())
-
-
-def transposed_table(idx, n0):
-    """cbl_neighbor_transpose's output, restated: for every target row t < n0 the ascending list of the pairs p = i * K + k whose neighbour is t (CSR: inv_start (n0 + 1),
-    inv_src); shadow neighbours (== n0) are in no list"""
-    flat = idx.reshape(-1)
-    keep = np.nonzero(flat < n0)[0]
-    order = np.argsort(flat[keep], kind="stable")
-    inv_src = keep[order].astype(np.int32)
-    inv_start = np.zeros(n0 + 1, np.int32)
-    np.add.at(inv_start, flat[keep] + 1, 1)
-    return np.cumsum(inv_start).astype(np.int32), inv_src
 
 
 @pytest.mark.parametrize("K,C,KP,influence,mode", [(16, 64, 15, "linear", "sum"), (26, 72, 15, "linear", "sum"), (9, 16, 7, "linear", "closest"), (40, 32, 15, "constant", "sum")])

@@ -4,41 +4,17 @@ path: K4 grouping_cuda_kernel.cu:16-25, the CBL gradient, KPConv / AdaptiveWeigh
 ASCENDING, the flat pair indices p = source * nsample + column with idx[p] == order_dst[r]; shadow entries are in no list.  The table bit for bit — hub targets
 (lists longer than a wave), targets nobody lists, a processing order, K on both sides of the per-thread batch sizes — and K4 over it against the oracle."""
 import ctypes
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import oracle_lib as O
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "contrastboundary_amd", "csrc")
-EMUL = os.path.join(HERE, "host_emul", "wave")
-GEN = os.path.join(HERE, "host_emul", "host_tu.py")
-TU = os.path.join(ROOT, "oracle", "_build", "neighbor_transpose_host.cpp")
-SO = os.path.join(ROOT, "oracle", "_build", "libneighbor_transpose_host.so")
+from tests.host_emul.host_build import P, load
 
 
 @pytest.fixture(scope="module")
 def host():
-    srcs = [os.path.join(CSRC, "neighbor_transpose.hip")]
-    deps = srcs + [GEN, os.path.abspath(__file__), os.path.join(CSRC, "cbl_common.h"), os.path.join(CSRC, "k4_rows_pipe.h"), os.path.join(EMUL, "gather_wave.h"),
-                   os.path.join(EMUL, "amdgcn.h"), os.path.join(EMUL, "hip", "hip_runtime.h")]
-    os.makedirs(os.path.dirname(SO), exist_ok=True)
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call([sys.executable, GEN, TU] + srcs)
-        subprocess.check_call(["g++", "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                               "-I" + EMUL, "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, TU, "-o", SO])
-    L = ctypes.CDLL(SO)
-    L.cbl_neighbor_transpose_workspace_bytes.restype = ctypes.c_size_t
-    return L
-
-
-def P(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+    return load("neighbor_transpose", ["neighbor_transpose"])
 
 
 def contract(idx, n, order_dst=None):

@@ -3,49 +3,16 @@ interpolation, subtraction, aggregation; /root/reference/pytorch/lib/pointops/sr
 functions/pointops.py:95-127) compiled for the HOST and run with wave semantics (tests/host_emul/wave), through their C entry points, against the oracle
 (oracle/pointops_oracle.c, pinned by the reference kernels' own outputs: tests/golden/pointops_*.npz): forward passes bit for bit (they copy, subtract or accumulate
 in the reference's order), scatter-form backward passes within the order of float atomics."""
-import ctypes
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 from tests import oracle_lib as O
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "contrastboundary_amd", "csrc")
-EMUL = os.path.join(HERE, "host_emul", "wave")
-GEN = os.path.join(HERE, "host_emul", "host_tu.py")
-TU = os.path.join(ROOT, "oracle", "_build", "pointops_gather_host.cpp")
-SO = os.path.join(ROOT, "oracle", "_build", "libpointops_gather_host.so")
+from tests.host_emul.host_build import P, aligned, load
 
 
 @pytest.fixture(scope="module")
 def host():
-    srcs = [os.path.join(CSRC, "pointops_gather.hip")]
-    deps = srcs + [GEN, os.path.abspath(__file__), os.path.join(CSRC, "cbl_common.h"), os.path.join(CSRC, "query_group_pipe.h"), os.path.join(EMUL, "gather_wave.h"),
-                   os.path.join(EMUL, "amdgcn.h"), os.path.join(EMUL, "hip", "hip_runtime.h")]
-    os.makedirs(os.path.dirname(SO), exist_ok=True)
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call([sys.executable, GEN, TU] + srcs)
-        subprocess.check_call(["g++", "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                               "-I" + EMUL, "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, TU, "-o", SO])
-    return ctypes.CDLL(SO)
-
-
-def P(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
-
-
-def aligned(a):
-    a = np.ascontiguousarray(a)
-    raw = np.zeros(a.nbytes + 16, np.uint8)
-    off = (-raw.ctypes.data) % 16
-    out = raw[off:off + a.nbytes].view(a.dtype).reshape(a.shape)
-    out[...] = a
-    return out
+    return load("pointops_gather", ["pointops_gather"])
 
 
 def scene(n, m, K, c, seed):

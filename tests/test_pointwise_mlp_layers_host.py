@@ -9,78 +9,21 @@ buffers of exactly their logical size: an indexing error of a kernel surfaces th
 import ctypes
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import pointwise_mlp_layers_oracle as O
+from tests.host_emul.host_build import BUILD, HERE, INCLUDES, P, aligned, dependencies, load, nans, stale, translation_unit, transposed_table
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "contrastboundary_amd", "csrc")
-EMUL = os.path.join(HERE, "host_emul", "wave")
-GEN = os.path.join(HERE, "host_emul", "host_tu.py")
-BUILD = os.path.join(ROOT, "oracle", "_build")
-TU = os.path.join(BUILD, "pointwise_mlp_layers_host.cpp")
-SO = os.path.join(BUILD, "libpointwise_mlp_layers_host.so")
-ASAN_MAIN = os.path.join(HERE, "host_emul", "pointwise_mlp_layers_asan_main.cpp")
+ASAN_MAIN = os.path.join(HERE, "pointwise_mlp_layers_asan_main.cpp")
 ASAN_EXE = os.path.join(BUILD, "pointwise_mlp_layers_asan")
-SRCS = [os.path.join(CSRC, "pointwise_mlp_layers.hip")]
-DEPS = SRCS + [GEN, os.path.abspath(__file__), os.path.join(CSRC, "cbl_common.h"), os.path.join(CSRC, "pair_tile.h"), os.path.join(ROOT, "include", "cbl_amd.h"),
-               os.path.join(EMUL, "amdgcn.h"), os.path.join(EMUL, "hip", "hip_runtime.h")]
-INCLUDES = ["-I" + EMUL, "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
 cf = ctypes.c_float
-
-
-def stale(target, deps):
-    return not os.path.exists(target) or os.path.getmtime(target) < max(os.path.getmtime(d) for d in deps)
-
-
-def generate():
-    os.makedirs(BUILD, exist_ok=True)
-    if stale(TU, DEPS):
-        subprocess.check_call([sys.executable, GEN, TU] + SRCS)
 
 
 @pytest.fixture(scope="module")
 def host():
-    generate()
-    if stale(SO, DEPS + [TU]):
-        subprocess.check_call(["g++", "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas"] + INCLUDES +
-                              [TU, "-o", SO])
-    L = ctypes.CDLL(SO)
-    L.cbl_pointwise_mlp_layers_workspace_bytes.restype = ctypes.c_size_t
-    return L
-
-
-def P(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
-
-
-def aligned(a):
-    """a copy of `a` whose data pointer is 16-byte aligned"""
-    a = np.ascontiguousarray(a)
-    raw = np.zeros(a.nbytes + 16, np.uint8)
-    off = (-raw.ctypes.data) % 16
-    out = raw[off:off + a.nbytes].view(a.dtype).reshape(a.shape)
-    out[...] = a
-    return out
-
-
-def nans(*shape):
-    return aligned(np.full(shape, np.nan, np.float32))
-
-
-def transposed_table(idx, n0):
-    """cbl_neighbor_transpose's output, restated (as tests/test_local_aggregation_host.py)"""
-    flat = idx.reshape(-1)
-    keep = np.nonzero(flat < n0)[0]
-    order = np.argsort(flat[keep], kind="stable")
-    inv_src = keep[order].astype(np.int32)
-    inv_start = np.zeros(n0 + 1, np.int32)
-    np.add.at(inv_start, flat[keep] + 1, 1)
-    return np.cumsum(inv_start).astype(np.int32), inv_src
+    return load("pointwise_mlp_layers", ["pointwise_mlp_layers"])
 
 
 def fold(case):
@@ -342,8 +285,8 @@ def test_the_mirror_refuses_what_the_kernels_do_not_cover():
 def test_the_kernels_under_address_sanitizer():
     """the stand-alone program: the same translation unit with -fsanitize=address,undefined, forward + backward over the shape edges, heap buffers of exactly
     their logical size"""
-    generate()
-    if stale(ASAN_EXE, DEPS + [TU, ASAN_MAIN]):
+    tu = translation_unit("pointwise_mlp_layers")                        # the program's main includes it by name, from BUILD
+    if stale(ASAN_EXE, dependencies(["pointwise_mlp_layers"]) + [tu, ASAN_MAIN]):
         subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-ffp-contract=off",
                                "-Wno-unknown-pragmas"] + INCLUDES + ["-I" + BUILD, ASAN_MAIN, "-o", ASAN_EXE])
     # (the emulator keeps its fibre stacks for the life of the process: no leak report)

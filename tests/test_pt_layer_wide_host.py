@@ -3,56 +3,17 @@ native host code issuing the kernels of attention.hip, the p chain of pt_layer.h
 three coarse stages) compiled for the HOST and run with wave semantics (tests/host_emul/wave), against the layer's formula in float64 differentiated by autograd
 (the reference function of tests/test_pt_layer_host.py): saved tensors, output, running statistics, the gradient of every input and parameter."""
 import ctypes
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+from tests.host_emul.host_build import P, aligned, load
 from tests.test_pt_layer_host import EPS, PARAMS, make, reference, rel
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "contrastboundary_amd", "csrc")
-EMUL = os.path.join(HERE, "host_emul", "wave")
-GEN = os.path.join(HERE, "host_emul", "host_tu.py")
-BUILD = os.path.join(ROOT, "oracle", "_build")
-SO = os.path.join(BUILD, "libpt_layer_wide_host.so")
 
 
 @pytest.fixture(scope="module")
 def host():
-    srcs = {"pt_layer": os.path.join(CSRC, "pt_layer.hip"), "attention": os.path.join(CSRC, "attention.hip")}
-    deps = list(srcs.values()) + [GEN, os.path.abspath(__file__), os.path.join(CSRC, "cbl_common.h"), os.path.join(EMUL, "pt_wave.h"), os.path.join(EMUL, "amdgcn.h"),
-                                  os.path.join(EMUL, "hip", "hip_runtime.h")]
-    os.makedirs(BUILD, exist_ok=True)
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-        objs = []
-        for name, src in srcs.items():
-            tu, obj = os.path.join(BUILD, name + "_widehost.cpp"), os.path.join(BUILD, name + "_widehost.o")
-            # pt_layer.hip WITH its wide-stage section (its older host build stops in front of it)
-            subprocess.check_call([sys.executable, GEN] + (["--whole"] if name == "pt_layer" else []) + [tu, src])
-            subprocess.check_call(["g++", "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-c", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                                   "-I" + EMUL, "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, tu, "-o", obj])
-            objs.append(obj)
-        subprocess.check_call(["g++", "-shared"] + objs + ["-o", SO])
-    L = ctypes.CDLL(SO)
-    L.cbl_pt_layer_wide_workspace_bytes.restype = ctypes.c_size_t
-    return L
-
-
-def P(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
-
-
-def aligned(a):
-    a = np.ascontiguousarray(a)
-    raw = np.zeros(a.nbytes + 16, np.uint8)
-    off = (-raw.ctypes.data) % 16
-    out = raw[off:off + a.nbytes].view(a.dtype).reshape(a.shape)
-    out[...] = a
-    return out
+    return load("pt_layer_wide", ["pt_layer", "attention"], whole=["pt_layer"])
 
 
 @pytest.mark.parametrize("n,K,C", [(40, 16, 128), (23, 16, 256), (35, 8, 128), (17, 16, 512)])

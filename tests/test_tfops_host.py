@@ -5,50 +5,20 @@ through `cbl_grid_subsampling` / `cbl_radius_neighbors`, against the oracle (ora
 barycentres, voxel counts, features and majority labels bit for bit in the canonical order; neighbour tables, counts and the largest neighbourhood bit for bit.
 The whole input pyramid as one native call (pyramid.hip: `cbl_pyramid`, datasets/base.py:767-842) against the oracle's operators applied layer by layer."""
 import ctypes
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from contrastboundary_amd import synthetic as S
 from tests import oracle_lib as O
+from tests.host_emul.host_build import P, load
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "contrastboundary_amd", "csrc")
-EMUL = os.path.join(HERE, "host_emul", "wave")
-GEN = os.path.join(HERE, "host_emul", "host_tu.py")
-BUILD = os.path.join(ROOT, "oracle", "_build")
-SO = os.path.join(BUILD, "libtfops_host.so")
 FILES = ["tfops", "pyramid", "knn_grid", "knn_exact", "knn_select", "knn_dispatch"]
 
 
 @pytest.fixture(scope="module")
 def host():
-    srcs = [os.path.join(CSRC, f + ".hip") for f in FILES]
-    deps = srcs + [GEN, os.path.abspath(__file__), os.path.join(CSRC, "cbl_common.h"), os.path.join(CSRC, "grid_core.h"), os.path.join(EMUL, "amdgcn.h"),
-                   os.path.join(EMUL, "hip", "hip_runtime.h"), os.path.join(EMUL, "rocprim", "device", "device_radix_sort.hpp")]
-    os.makedirs(BUILD, exist_ok=True)
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-        objs = []
-        for f, src in zip(FILES, srcs):
-            tu, obj = os.path.join(BUILD, f + "_host.cpp"), os.path.join(BUILD, f + "_tfhost.o")
-            subprocess.check_call([sys.executable, GEN, tu, src])
-            subprocess.check_call(["g++", "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-c", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                                   "-I" + EMUL, "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, tu, "-o", obj])
-            objs.append(obj)
-        subprocess.check_call(["g++", "-shared"] + objs + ["-o", SO])
-    L = ctypes.CDLL(SO)
-    L.cbl_grid_subsampling_workspace_bytes.restype = ctypes.c_size_t
-    L.cbl_radius_neighbors_workspace_bytes.restype = ctypes.c_size_t
-    L.cbl_pyramid_layer_workspace_bytes.restype = ctypes.c_size_t
-    return L
-
-
-def P(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+    return load("tfops", FILES)
 
 
 @pytest.mark.parametrize("dl", [0.08, 0.3])

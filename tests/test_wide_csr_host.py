@@ -5,62 +5,20 @@ table instead of float atomics — compiled for the HOST and run with wave seman
 numpy, independent of neighbor_transpose.hip.  Every neighbour table holds a target no pair lists, a hub listed by more than 3 K pairs (a count that is no
 multiple of 4, the gathers' unroll) and a row that lists one point K times."""
 import ctypes
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+from tests.host_emul.host_build import P, aligned
 from tests.test_attention_host import close
 from tests.test_pt_layer_host import EPS, PARAMS, make, reference, rel
+from tests.test_pt_layer_wide_host import host  # noqa: F401  (the fixture that builds and loads the host library)
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "contrastboundary_amd", "csrc")
-EMUL = os.path.join(HERE, "host_emul", "wave")
-GEN = os.path.join(HERE, "host_emul", "host_tu.py")
-BUILD = os.path.join(ROOT, "oracle", "_build")
-SO = os.path.join(BUILD, "libwide_csr_host.so")
 F = ctypes.c_float
 
 SHAPES = [(40, 16, 128), (35, 8, 128), (23, 16, 256), (17, 16, 512), (29, 5, 128)]     # the last: a ragged K against the 16-pair tile
 HUB, REPEATED, REPEATED_ROW = 2, 7, lambda n: n // 3                                    # the unlisted target is n - 1
-
-
-@pytest.fixture(scope="module")
-def host():
-    srcs = {"pt_layer": os.path.join(CSRC, "pt_layer.hip"), "attention": os.path.join(CSRC, "attention.hip")}
-    deps = list(srcs.values()) + [GEN, os.path.abspath(__file__), os.path.join(CSRC, "cbl_common.h"), os.path.join(EMUL, "pt_wave.h"), os.path.join(EMUL, "amdgcn.h"),
-                                  os.path.join(EMUL, "hip", "hip_runtime.h"), os.path.join(ROOT, "include", "cbl_amd.h")]
-    os.makedirs(BUILD, exist_ok=True)
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-        objs = []
-        for name, src in srcs.items():
-            tu, obj = os.path.join(BUILD, name + "_widecsrhost.cpp"), os.path.join(BUILD, name + "_widecsrhost.o")
-            subprocess.check_call([sys.executable, GEN] + (["--whole"] if name == "pt_layer" else []) + [tu, src])
-            subprocess.check_call(["g++", "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-c", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                                   "-I" + EMUL, "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, tu, "-o", obj])
-            objs.append(obj)
-        subprocess.check_call(["g++", "-shared"] + objs + ["-o", SO])
-    L = ctypes.CDLL(SO)
-    L.cbl_pt_layer_wide_workspace_bytes.restype = ctypes.c_size_t
-    L.cbl_attn_workspace_bytes.restype = ctypes.c_size_t
-    return L
-
-
-def P(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
-
-
-def aligned(a):
-    a = np.ascontiguousarray(a)
-    raw = np.zeros(a.nbytes + 16, np.uint8)
-    off = (-raw.ctypes.data) % 16
-    out = raw[off:off + a.nbytes].view(a.dtype).reshape(a.shape)
-    out[...] = a
-    return out
 
 
 def neighbours(n, K, rng):
