@@ -1,0 +1,155 @@
+"""The ConvNet's unary layer conv1d_1x1 (tensorflow/models/basic_operators.py:195-241): matmul in TF's (in, out) weight order, optional bias, TF batch norm
+(biased variance, moving = moving * momentum + batch * (1 - momentum)), an optional shortcut added before the activation (the tail of a bottleneck,
+backbone/resnet.py:158-192), relu / leaky_relu(0.2) / none — the two entries of csrc/unary_layer.hip (cbl_amd.h, a15 conv1d_1x1) under autograd.  There is no
+fallback: CPU tensors raise, widths past 4096 raise."""
+import ctypes
+
+import torch
+from torch.autograd import Function
+
+from . import _lib
+from .local_aggregation import _fan_in_init_
+
+_i = ctypes.c_int
+_f = ctypes.c_float
+_ll = ctypes.c_longlong
+_ACTIVATIONS = {"relu": 1, "leaky_relu": 2}              # any other string is the identity (basic_operators.py:237-241)
+MAX_WIDTH = 4096
+
+
+def _chk(t, name):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+        raise TypeError(f"{name}: expected a contiguous CUDA tensor of torch.float32")
+    return t
+
+
+def _workspace(L, rows, c_in, c_out, dev):
+    return torch.empty(max(L.cbl_unary_layer_workspace_bytes(_ll(rows), _i(c_in), _i(c_out)), 1), dtype=torch.uint8, device=dev)
+
+
+class _Conv1d1x1(Function):
+    @staticmethod
+    def forward(ctx, features, weights, biases, gamma, beta, shortcut, moving, bn_mode, act, momentum, eps):
+        # moving: the tuple (moving_mean, moving_variance), which the kernels update in place under bn_mode 1.  They are buffers, not inputs of the
+        # differentiated function, so they travel as one plain Python object and autograd never sees an input modified in place
+        moving_mean, moving_variance = moving
+        L = _lib.lib()
+        rows, c_in = features.shape
+        c_out = weights.shape[1]
+        dev = features.device
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        out = new(rows, c_out)
+        y = new(rows, c_out) if bn_mode else None
+        save_mean, save_invstd = (new(c_out), new(c_out)) if bn_mode else (None, None)
+        ws = _workspace(L, rows, c_in, c_out, dev) if bn_mode == 1 else None
+        _lib.check(L.cbl_unary_layer_forward(_ll(rows), _i(c_in), _i(c_out), _lib.ptr(features), _lib.ptr(weights), _lib.ptr(biases), _lib.ptr(shortcut),
+                                             _i(bn_mode), _lib.ptr(gamma), _lib.ptr(beta), _f(eps), _f(momentum), _lib.ptr(moving_mean),
+                                             _lib.ptr(moving_variance), _i(act), _lib.ptr(save_mean), _lib.ptr(save_invstd), _lib.ptr(y), _lib.ptr(out),
+                                             _lib.ptr(ws), ctypes.c_size_t(ws.numel() if ws is not None else 0), _lib.stream_of(features)),
+                   "cbl_unary_layer_forward")
+        ctx.save_for_backward(features, weights, gamma, save_mean, save_invstd, y, out)
+        ctx.cfg = (bn_mode, act, biases is not None, shortcut is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        features, weights, gamma, save_mean, save_invstd, y, out = ctx.saved_tensors
+        bn_mode, act, has_bias, has_shortcut = ctx.cfg
+        L = _lib.lib()
+        rows, c_in = features.shape
+        c_out = weights.shape[1]
+        dev = features.device
+        grad_out = grad_out.contiguous()
+        need = ctx.needs_input_grad
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        gx = new(rows, c_in) if need[0] else None
+        gw = new(c_in, c_out) if need[1] else None
+        gb = new(c_out) if has_bias and need[2] else None
+        gg = new(c_out) if bn_mode and need[3] else None
+        gbeta = new(c_out) if bn_mode and need[4] else None
+        gs = new(rows, c_out) if has_shortcut and need[5] else None
+        if rows == 0:
+            for g in (gw, gb, gg, gbeta):
+                if g is not None:
+                    g.zero_()
+            return (gx, gw, gb, gg, gbeta, gs) + (None,) * 5
+        ws = _workspace(L, rows, c_in, c_out, dev)
+        _lib.check(L.cbl_unary_layer_backward(_ll(rows), _i(c_in), _i(c_out), _lib.ptr(features), _lib.ptr(weights), _i(bn_mode), _lib.ptr(gamma),
+                                              _lib.ptr(save_mean), _lib.ptr(save_invstd), _i(act), _lib.ptr(y), _lib.ptr(out), _lib.ptr(grad_out),
+                                              _lib.ptr(gx), _lib.ptr(gw), _lib.ptr(gb), _lib.ptr(gg), _lib.ptr(gbeta), _lib.ptr(gs), _lib.ptr(ws),
+                                              ctypes.c_size_t(ws.numel()), _lib.stream_of(features)), "cbl_unary_layer_backward")
+        return (gx, gw, gb, gg, gbeta, gs) + (None,) * 5
+
+
+def conv1d_1x1(features, weights, biases=None, gamma=None, beta=None, moving_mean=None, moving_variance=None, *, is_training=True, activation_fn="relu",
+               bn_momentum=0.98, bn_eps=1e-3, shortcut=None):
+    """act(bn(features @ weights (+ biases)) (+ shortcut))  (rows, c_out)  (basic_operators.py:195-241).  weights: the TF variable (c_in, c_out); biases:
+    with_bias; gamma / beta: the batch norm (gamma None: bn=False); moving_mean / moving_variance: updated in place when training (TF convention), used when
+    not; shortcut (rows, c_out): added before the activation, which makes one call the tail of a bottleneck.  Runs on the current stream of the tensors'
+    device; 1 <= c_in, c_out <= 4096."""
+    _chk(features, "features"); _chk(weights, "weights")
+    for t, name in ((biases, "biases"), (gamma, "gamma"), (beta, "beta"), (moving_mean, "moving_mean"), (moving_variance, "moving_variance"),
+                    (shortcut, "shortcut")):
+        if t is not None:
+            _chk(t, name)
+    if features.dim() != 2 or weights.dim() != 2 or features.shape[1] != weights.shape[0]:
+        raise ValueError("conv1d_1x1: features {} and weights {}: (rows, c_in) and (c_in, c_out) expected".format(tuple(features.shape), tuple(weights.shape)))
+    c_in, c_out = weights.shape
+    if not (1 <= c_in <= MAX_WIDTH and 1 <= c_out <= MAX_WIDTH):
+        raise NotImplementedError("conv1d_1x1: widths {} -> {} (1 to {} each)".format(c_in, c_out, MAX_WIDTH))
+    if (gamma is None) != (beta is None):
+        raise ValueError("conv1d_1x1: gamma and beta come together (both None: bn=False)")
+    if gamma is None and (moving_mean is not None or moving_variance is not None):
+        raise ValueError("conv1d_1x1: moving statistics without a batch norm")
+    if (moving_mean is None) != (moving_variance is None):
+        raise ValueError("conv1d_1x1: moving_mean and moving_variance come together")
+    if gamma is not None and not is_training and moving_mean is None:
+        raise ValueError("conv1d_1x1: is_training=False needs moving_mean and moving_variance")
+    for t, name in ((biases, "biases"), (gamma, "gamma"), (beta, "beta"), (moving_mean, "moving_mean"), (moving_variance, "moving_variance")):
+        if t is not None and tuple(t.shape) != (c_out,):
+            raise ValueError("conv1d_1x1: {} of shape {}, ({},) expected".format(name, tuple(t.shape), c_out))
+    if shortcut is not None and tuple(shortcut.shape) != (features.shape[0], c_out):
+        raise ValueError("conv1d_1x1: shortcut of shape {}, ({}, {}) expected".format(tuple(shortcut.shape), features.shape[0], c_out))
+    bn_mode = 0 if gamma is None else (1 if is_training else 2)
+    return _Conv1d1x1.apply(features, weights, biases, gamma, beta, shortcut, (moving_mean, moving_variance), bn_mode, _ACTIVATIONS.get(activation_fn, 0),
+                            float(bn_momentum), float(bn_eps))
+
+
+class Conv1d1x1(torch.nn.Module):
+    """conv1d_1x1 with the reference's variables (TF names): `weights` (in_fdim, out_fdim) — init 'xavier' (glorot uniform, the default) or 'fan_in' —,
+    `biases` (zeros; with_bias), and under bn `gamma` (ones), `beta` (zeros) and the buffers `moving_mean` (zeros) / `moving_variance` (ones)"""
+
+    def __init__(self, in_fdim, out_fdim, with_bias=False, init="xavier", activation_fn="relu", bn=True, bn_momentum=0.98, bn_eps=1e-3, scope=""):
+        super().__init__()
+        if not (1 <= in_fdim <= MAX_WIDTH and 1 <= out_fdim <= MAX_WIDTH):
+            raise NotImplementedError("Conv1d1x1: widths {} -> {} (1 to {} each)".format(in_fdim, out_fdim, MAX_WIDTH))
+        if init not in ("xavier", "fan_in"):
+            raise NotImplementedError("Conv1d1x1: init {} ('xavier' or 'fan_in')".format(init))
+        self.activation_fn, self.bn_momentum, self.bn_eps, self.scope = activation_fn, bn_momentum, bn_eps, scope
+        self.weights = torch.nn.Parameter(torch.empty(in_fdim, out_fdim))
+        if init == "xavier":
+            torch.nn.init.xavier_uniform_(self.weights)
+        else:
+            _fan_in_init_(self.weights)
+        self.biases = torch.nn.Parameter(torch.zeros(out_fdim)) if with_bias else None
+        if bn:
+            self.gamma = torch.nn.Parameter(torch.ones(out_fdim))
+            self.beta = torch.nn.Parameter(torch.zeros(out_fdim))
+            self.register_buffer("moving_mean", torch.zeros(out_fdim))
+            self.register_buffer("moving_variance", torch.ones(out_fdim))
+        else:
+            self.gamma = self.beta = self.moving_mean = self.moving_variance = None
+
+    def tf_scopes(self):
+        """variable name -> its TF variable scope (:223-235): weights / biases in the layer's own scope, the batch norm's variables under bn/"""
+        bn = (self.scope + "/bn") if self.scope else "bn"
+        names = {"weights": self.scope}
+        if self.biases is not None:
+            names["biases"] = self.scope
+        if self.gamma is not None:
+            names.update(gamma=bn, beta=bn, moving_mean=bn, moving_variance=bn)
+        return names
+
+    def forward(self, features, shortcut=None):
+        return conv1d_1x1(features, self.weights, self.biases, self.gamma, self.beta, self.moving_mean, self.moving_variance, is_training=self.training,
+                          activation_fn=self.activation_fn, bn_momentum=self.bn_momentum, bn_eps=self.bn_eps, shortcut=shortcut)

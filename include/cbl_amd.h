@@ -587,6 +587,37 @@ int cbl_pointwise_mlp_layers_backward_csr(int n, int n0, int K, int H, int C_out
                                           float* grad_center, float* grad_neighbor, float* grad_w_pos, float* grad_hidden_w, float* grad_gamma,
                                           float* grad_beta, void* workspace, size_t workspace_bytes, void* stream);
 
+/* a15  conv1d_1x1  tensorflow/models/basic_operators.py:195-241, the ConvNet's unary layer (every bottleneck conv, the input conv, the head's up_conv*,
+ *   segmentation_head and segmentation_pred): for x (rows,c_in), weights (c_in,c_out) in TF's (in,out) order, biases (c_out) or NULL (with_bias, :229-233)
+ *       y = x @ weights (+ biases)        z = bn(y) (+ shortcut)        out = act(z)
+ *   shortcut (rows,c_out) or NULL: with it one call is the tail of a bottleneck, act(bn(conv3) + shortcut) (backbone/resnet.py:158-192).
+ *   bn_mode: 0 none | 1 batch statistics over all rows (biased variance; moving_mean / moving_var, when given (both or neither), updated the TF way:
+ *            moving = moving * momentum + batch * (1 - momentum), biased variance) | 2 moving statistics (no buffer is written).  Modes 1 and 2 leave the
+ *            mean / invstd used in save_mean / save_invstd (c_out), which the backward call takes back; they need gamma and beta.
+ *   activation: 0 none | 1 relu | 2 leaky_relu(0.2).
+ *   y (rows,c_out): the product before the batch norm, kept for the backward call (which never recomputes it); may be NULL under bn_mode 0.
+ *   Any rows >= 0 (0: a no-op), 1 <= c_in, c_out <= 4096 (wider: CBL_ERR_UNSUPPORTED, and cbl_unary_layer_workspace_bytes returns 0).  No alignment is
+ *   required beyond a float's: widths that are no multiple of 4 and bases that are not 16-byte aligned are read with scalar loads.  Bad arguments (a NULL
+ *   input, a mode outside its range, batch-norm variables missing under bn_mode 1 / 2 or grad_gamma / grad_beta given under bn_mode 0) return
+ *   CBL_ERR_BAD_ARG before any launch, a short workspace CBL_ERR_WORKSPACE (one size for both calls; the forward call needs it under bn_mode 1 only).
+ *   The three products run on v_mfma_f32_16x16x4_f32 (exact fp32 chains).  No float atomics: every output is stored once in a fixed summation order (two
+ *   calls give the same bits); no allocation or synchronisation inside a call. */
+size_t cbl_unary_layer_workspace_bytes(long long rows, int c_in, int c_out);
+int cbl_unary_layer_forward(long long rows, int c_in, int c_out, const float* x, const float* weights, const float* biases, const float* shortcut,
+                            int bn_mode, const float* gamma, const float* beta, float eps, float momentum, float* moving_mean, float* moving_var,
+                            int activation, float* save_mean, float* save_invstd, float* y, float* out,
+                            void* workspace, size_t workspace_bytes, void* stream);
+/* gradients (any may be NULL), all WRITTEN: grad_x (rows,c_in) = dy @ weights^T, grad_weights (c_in,c_out) = x^T @ dy, grad_biases (c_out) = sum_rows dy,
+ * grad_gamma = sum dz * xhat, grad_beta = sum dz (c_out; bn_mode 1 and 2), grad_shortcut (rows,c_out) = dz.  dz = grad_out * act'(out) — the mask is
+ * out > 0, which is z > 0 for both activations, so the shortcut is not read again (out may be NULL with activation 0); dy = dz through the batch norm
+ * (bn_mode 1: dy = gamma * invstd * (dz - sum dz / N - xhat * sum(dz * xhat) / N), N = rows; bn_mode 2: gamma * invstd * dz).  y, save_mean, save_invstd: as
+ * the forward call left them. */
+int cbl_unary_layer_backward(long long rows, int c_in, int c_out, const float* x, const float* weights,
+                             int bn_mode, const float* gamma, const float* save_mean, const float* save_invstd, int activation,
+                             const float* y, const float* out, const float* grad_out,
+                             float* grad_x, float* grad_weights, float* grad_biases, float* grad_gamma, float* grad_beta, float* grad_shortcut,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
 /* a4  PointTransformerLayer pytorch/model/blocks.py:31-44, the C-wide part without its (n,K,C) tensors (C = 32 or 64, G = C/8):
  *   p1 (n,K,3) = ReLU(BN(Linear(3,3)(p_j - p_i)))  [computed by the caller: narrow],  p_r = Linear(3,C)(p1) = p1 @ W3C^T + b3C  [never stored]
  * attn_w2:  w2 (n,K,G) = Linear(C,G)( ReLU( BN_C( x_k[idx] - x_q + p_r ) ) )       (:39 and the first half of linear_w, :25-27)
