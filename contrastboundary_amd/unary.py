@@ -1,14 +1,16 @@
 """The ConvNet's unary layer conv1d_1x1 (tensorflow/models/basic_operators.py:195-241): matmul in TF's (in, out) weight order, optional bias, TF batch norm
 (biased variance, moving = moving * momentum + batch * (1 - momentum)), an optional shortcut added before the activation (the tail of a bottleneck,
 backbone/resnet.py:158-192), relu / leaky_relu(0.2) / none — the two entries of csrc/unary_layer.hip (cbl_amd.h, a15 conv1d_1x1) under autograd.  There is no
-fallback: CPU tensors raise, widths past 4096 raise."""
+fallback: CPU tensors raise, widths past 4096 raise.
+up_conv / UpConv1d1x1: one decoder step of the segmentation head (models/heads/seg_head.py:63-67), nearest upsample + concat + conv1d_1x1 without the upsampled
+and the concatenated tensor (cbl_up_conv_*, csrc/up_conv.hip)."""
 import ctypes
 
 import torch
 from torch.autograd import Function
 
 from . import _lib
-from .local_aggregation import _fan_in_init_
+from .local_aggregation import _fan_in_init_, _first_column
 
 _i = ctypes.c_int
 _f = ctypes.c_float
@@ -153,3 +155,122 @@ class Conv1d1x1(torch.nn.Module):
     def forward(self, features, shortcut=None):
         return conv1d_1x1(features, self.weights, self.biases, self.gamma, self.beta, self.moving_mean, self.moving_variance, is_training=self.training,
                           activation_fn=self.activation_fn, bn_momentum=self.bn_momentum, bn_eps=self.bn_eps, shortcut=shortcut)
+
+
+# ---------------------------------------------------------------------------------------------- the segmentation head's decoder step
+def _up_workspace(L, n2, n1, c_up, c_skip, c_out, dev):
+    return torch.empty(max(L.cbl_up_conv_workspace_bytes(_ll(n2), _ll(n1), _i(c_up), _i(c_skip), _i(c_out)), 1), dtype=torch.uint8, device=dev)
+
+
+class _UpConv(Function):
+    @staticmethod
+    def forward(ctx, coarse, inds, skip, weights, biases, gamma, beta, moving, bn_mode, act, momentum, eps):
+        # (moving: as in _Conv1d1x1)
+        moving_mean, moving_variance = moving
+        L = _lib.lib()
+        (n1, c_up), (n2, c_skip), c_out, k = coarse.shape, skip.shape, weights.shape[1], inds.shape[1]
+        dev = coarse.device
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        out = new(n2, c_out)
+        y = new(n2, c_out) if bn_mode else None
+        save_mean, save_invstd = (new(c_out), new(c_out)) if bn_mode else (None, None)
+        ws = _up_workspace(L, n2, n1, c_up, c_skip, c_out, dev)
+        _lib.check(L.cbl_up_conv_forward(_ll(n2), _ll(n1), _i(c_up), _i(c_skip), _i(c_out), _lib.ptr(coarse), _lib.ptr(inds), _i(k), _lib.ptr(skip),
+                                         _lib.ptr(weights), _lib.ptr(biases), _i(bn_mode), _lib.ptr(gamma), _lib.ptr(beta), _f(eps), _f(momentum),
+                                         _lib.ptr(moving_mean), _lib.ptr(moving_variance), _i(act), _lib.ptr(save_mean), _lib.ptr(save_invstd), _lib.ptr(y),
+                                         _lib.ptr(out), _lib.ptr(ws), ctypes.c_size_t(ws.numel()), _lib.stream_of(coarse)), "cbl_up_conv_forward")
+        # the table's first column as the tensor the transposed table is registered under: built once per table, found again by every later backward pass
+        ctx.save_for_backward(coarse, _first_column(inds), skip, weights, gamma, save_mean, save_invstd, y, out)
+        ctx.cfg = (bn_mode, act, biases is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        coarse, inds0, skip, weights, gamma, save_mean, save_invstd, y, out = ctx.saved_tensors
+        bn_mode, act, has_bias = ctx.cfg
+        L = _lib.lib()
+        (n1, c_up), (n2, c_skip), c_out = coarse.shape, skip.shape, weights.shape[1]
+        dev = coarse.device
+        grad_out = grad_out.contiguous()
+        need = ctx.needs_input_grad
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        gc = new(n1, c_up) if need[0] else None
+        gs = new(n2, c_skip) if need[2] else None
+        gw = new(c_up + c_skip, c_out) if need[3] else None
+        gb = new(c_out) if has_bias and need[4] else None
+        gg = new(c_out) if bn_mode and need[5] else None
+        gbeta = new(c_out) if bn_mode and need[6] else None
+        grads = (gc, None, gs, gw, gb, gg, gbeta) + (None,) * 5
+        if n2 == 0:
+            for g in (gc, gw, gb, gg, gbeta):
+                if g is not None:
+                    g.zero_()
+            return grads
+        order = inv_start = inv_src = None
+        if gc is not None or gw is not None:
+            from . import pointops
+            tr = pointops.neighbor_transpose(inds0, n1, build=True)     # shadow ids are in no segment: they receive nothing
+            if tr is None:
+                raise NotImplementedError("up_conv: no transposed table for {} coarse rows (cbl_neighbor_transpose's limit)".format(n1))
+            order, inv_start, inv_src = tr
+        ws = _up_workspace(L, n2, n1, c_up, c_skip, c_out, dev)
+        _lib.check(L.cbl_up_conv_backward(_ll(n2), _ll(n1), _i(c_up), _i(c_skip), _i(c_out), _lib.ptr(coarse), _lib.ptr(inds0), _i(inds0.shape[1]), _lib.ptr(skip),
+                                          _lib.ptr(weights), _i(bn_mode), _lib.ptr(gamma), _lib.ptr(save_mean), _lib.ptr(save_invstd), _i(act), _lib.ptr(y),
+                                          _lib.ptr(out), _lib.ptr(grad_out), _lib.ptr(order), _lib.ptr(inv_start), _lib.ptr(inv_src), _lib.ptr(gc), _lib.ptr(gs),
+                                          _lib.ptr(gw), _lib.ptr(gb), _lib.ptr(gg), _lib.ptr(gbeta), _lib.ptr(ws), ctypes.c_size_t(ws.numel()),
+                                          _lib.stream_of(coarse)), "cbl_up_conv_backward")
+        return grads
+
+
+def up_conv(coarse, upsample_inds, skip, weights, biases=None, gamma=None, beta=None, moving_mean=None, moving_variance=None, *, is_training=True,
+            activation_fn="relu", bn_momentum=0.98, bn_eps=1e-3):
+    """One decoder step of the segmentation head (models/heads/seg_head.py:63-67): conv1d_1x1(concat(nearest_upsample(coarse, upsample_inds), skip)) without
+    the upsampled and the concatenated tensor.  coarse (n1, c_up): the coarser layer's features; upsample_inds (n2, max_num) int32, of which column 0 is
+    read, an id outside [0, n1) selecting the zero row; skip (n2, c_skip): the encoder's features of the finer layer; weights: the ONE TF variable
+    (c_up + c_skip, c_out) of the layer.  Everything else as conv1d_1x1 (there is no shortcut: the head has none).  1 <= c_up, c_skip, c_out;
+    c_up + c_skip <= 4096, c_out <= 4096; n1 >= 1."""
+    _chk(coarse, "coarse"); _chk(skip, "skip"); _chk(weights, "weights")
+    if not (isinstance(upsample_inds, torch.Tensor) and upsample_inds.is_cuda and upsample_inds.dtype == torch.int32 and upsample_inds.is_contiguous()):
+        raise TypeError("upsample_inds: expected a contiguous CUDA tensor of torch.int32")
+    for t, name in ((biases, "biases"), (gamma, "gamma"), (beta, "beta"), (moving_mean, "moving_mean"), (moving_variance, "moving_variance")):
+        if t is not None:
+            _chk(t, name)
+    if coarse.dim() != 2 or skip.dim() != 2 or weights.dim() != 2 or upsample_inds.dim() != 2 or upsample_inds.shape[1] < 1:
+        raise ValueError("up_conv: coarse (n1, c_up), upsample_inds (n2, max_num), skip (n2, c_skip) and weights (c_up + c_skip, c_out) expected")
+    (n1, c_up), (n2, c_skip), (c_in, c_out) = coarse.shape, skip.shape, weights.shape
+    if upsample_inds.shape[0] != n2 or c_in != c_up + c_skip or n1 < 1:
+        raise ValueError("up_conv: coarse {}, upsample_inds {}, skip {} and weights {} do not fit".format(tuple(coarse.shape), tuple(upsample_inds.shape),
+                                                                                                           tuple(skip.shape), tuple(weights.shape)))
+    if not (c_up >= 1 and c_skip >= 1 and c_in <= MAX_WIDTH and 1 <= c_out <= MAX_WIDTH):
+        raise NotImplementedError("up_conv: widths {} + {} -> {} (each at least 1, {} at most in and out)".format(c_up, c_skip, c_out, MAX_WIDTH))
+    if n2 * upsample_inds.shape[1] >= 2 ** 31:
+        raise NotImplementedError("up_conv: an upsample table of {} entries (fewer than 2^31)".format(n2 * upsample_inds.shape[1]))
+    if (gamma is None) != (beta is None):
+        raise ValueError("up_conv: gamma and beta come together (both None: bn=False)")
+    if gamma is None and (moving_mean is not None or moving_variance is not None):
+        raise ValueError("up_conv: moving statistics without a batch norm")
+    if (moving_mean is None) != (moving_variance is None):
+        raise ValueError("up_conv: moving_mean and moving_variance come together")
+    if gamma is not None and not is_training and moving_mean is None:
+        raise ValueError("up_conv: is_training=False needs moving_mean and moving_variance")
+    for t, name in ((biases, "biases"), (gamma, "gamma"), (beta, "beta"), (moving_mean, "moving_mean"), (moving_variance, "moving_variance")):
+        if t is not None and tuple(t.shape) != (c_out,):
+            raise ValueError("up_conv: {} of shape {}, ({},) expected".format(name, tuple(t.shape), c_out))
+    bn_mode = 0 if gamma is None else (1 if is_training else 2)
+    return _UpConv.apply(coarse, upsample_inds, skip, weights, biases, gamma, beta, (moving_mean, moving_variance), bn_mode, _ACTIVATIONS.get(activation_fn, 0),
+                         float(bn_momentum), float(bn_eps))
+
+
+class UpConv1d1x1(Conv1d1x1):
+    """up_conv with the variables, initialisers and tf_scopes() of Conv1d1x1(c_up + c_skip, out_fdim): ONE `weights` of (c_up + c_skip, out_fdim), so that a
+    TF checkpoint of the layer loads unchanged"""
+
+    def __init__(self, c_up, c_skip, out_fdim, with_bias=False, init="xavier", activation_fn="relu", bn=True, bn_momentum=0.98, bn_eps=1e-3, scope=""):
+        if c_up < 1 or c_skip < 1:
+            raise NotImplementedError("UpConv1d1x1: widths {} + {} (each at least 1)".format(c_up, c_skip))
+        super().__init__(c_up + c_skip, out_fdim, with_bias, init, activation_fn, bn, bn_momentum, bn_eps, scope)
+        self.c_up, self.c_skip = c_up, c_skip
+
+    def forward(self, coarse, upsample_inds, skip):
+        return up_conv(coarse, upsample_inds, skip, self.weights, self.biases, self.gamma, self.beta, self.moving_mean, self.moving_variance,
+                       is_training=self.training, activation_fn=self.activation_fn, bn_momentum=self.bn_momentum, bn_eps=self.bn_eps)

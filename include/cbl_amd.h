@@ -618,6 +618,35 @@ int cbl_unary_layer_backward(long long rows, int c_in, int c_out, const float* x
                              float* grad_x, float* grad_weights, float* grad_biases, float* grad_gamma, float* grad_beta, float* grad_shortcut,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* a15  one decoder step of the segmentation head, tensorflow/models/heads/seg_head.py:63-67 (and :70-88): nearest_upsample_block (seg_head.py:13-28 =
+ *   ind_closest_pool, basic_operators.py:175-192), tf.concat and conv1d_1x1 (basic_operators.py:195-241), without the upsampled and the concatenated tensor:
+ *       y[i] = (coarse @ W_up)[idx[i]] + skip[i] @ W_skip (+ biases)        z = bn(y)        out = act(z)
+ *   coarse (n1,c_up): the coarser layer's features; up_inds (n2,k) int32, of which only column 0 is read (idx[i] = up_inds[i * k]); an id outside [0, n1)
+ *   selects the zero row (the shadow row ind_closest_pool appends) and receives no gradient; skip (n2,c_skip); weights (c_up + c_skip, c_out): the ONE TF
+ *   variable of the layer, W_up = its first c_up rows, W_skip the rest.  bn_mode, activation, gamma / beta, eps, momentum, moving_mean / moving_var,
+ *   save_mean / save_invstd and y (n2,c_out) are those of cbl_unary_layer_forward; the statistics are taken over the full y, as if the concatenation had
+ *   been formed.  There is no shortcut.
+ *   1 <= c_up, c_skip, c_out; c_up + c_skip <= 4096 and c_out <= 4096 (else CBL_ERR_UNSUPPORTED, and a workspace size of 0); n1 >= 1; n2 >= 0 (0: a no-op);
+ *   n2 * k < 2^31.  The workspace (one size for both calls) is needed by both calls under every bn_mode: it holds coarse @ W_up.  Error codes, alignment
+ *   (none beyond a float's), determinism (no float atomics, every output stored once, grids from the shapes alone) and capture: as the unary entries.
+ *   Where the 64 x 64 tiles of a product at the coarse layer's n1 rows (coarse @ W_up, grad_coarse) are at most half of 256 compute units and its contraction
+ *   is at least 8 panels of 64 steps long, the contraction is split over up to 8 workgroups per tile, whose partials are summed in split order in fp64: a rule
+ *   on the shapes alone.  (Measurement knob: the environment variable CBL_UP_CONV_SPLIT=0, read at every call, switches the split off.) */
+size_t cbl_up_conv_workspace_bytes(long long n2, long long n1, int c_up, int c_skip, int c_out);
+int cbl_up_conv_forward(long long n2, long long n1, int c_up, int c_skip, int c_out, const float* coarse, const int* up_inds, int k, const float* skip,
+                        const float* weights, const float* biases, int bn_mode, const float* gamma, const float* beta, float eps, float momentum,
+                        float* moving_mean, float* moving_var, int activation, float* save_mean, float* save_invstd, float* y, float* out,
+                        void* workspace, size_t workspace_bytes, void* stream);
+/* gradients (any may be NULL), all WRITTEN.  order / inv_start / inv_src: cbl_neighbor_transpose's table of up_inds' FIRST COLUMN (n2 sources, one column)
+ * over n1 targets (order may be NULL); needed for grad_coarse and grad_weights.  With dy as in cbl_unary_layer_backward and dyc[j] = the sum of dy[i] over
+ * {i : idx[i] == j} in ascending i (zeros for a coarse row nobody references):  grad_coarse (n1,c_up) = dyc @ W_up^T, grad_skip (n2,c_skip) = dy @ W_skip^T,
+ * grad_weights (c_up + c_skip, c_out) = [coarse^T @ dyc; skip^T @ dy], grad_biases = sum_rows dy, grad_gamma, grad_beta.  up_inds itself is not read. */
+int cbl_up_conv_backward(long long n2, long long n1, int c_up, int c_skip, int c_out, const float* coarse, const int* up_inds, int k, const float* skip,
+                         const float* weights, int bn_mode, const float* gamma, const float* save_mean, const float* save_invstd, int activation,
+                         const float* y, const float* out, const float* grad_out, const int* order, const int* inv_start, const int* inv_src,
+                         float* grad_coarse, float* grad_skip, float* grad_weights, float* grad_biases, float* grad_gamma, float* grad_beta,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* a4  PointTransformerLayer pytorch/model/blocks.py:31-44, the C-wide part without its (n,K,C) tensors (C = 32 or 64, G = C/8):
  *   p1 (n,K,3) = ReLU(BN(Linear(3,3)(p_j - p_i)))  [computed by the caller: narrow],  p_r = Linear(3,C)(p1) = p1 @ W3C^T + b3C  [never stored]
  * attn_w2:  w2 (n,K,G) = Linear(C,G)( ReLU( BN_C( x_k[idx] - x_q + p_r ) ) )       (:39 and the first half of linear_w, :25-27)
