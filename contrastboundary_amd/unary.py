@@ -3,7 +3,9 @@
 backbone/resnet.py:158-192), relu / leaky_relu(0.2) / none — the two entries of csrc/unary_layer.hip (cbl_amd.h, a15 conv1d_1x1) under autograd.  There is no
 fallback: CPU tensors raise, widths past 4096 raise.
 up_conv / UpConv1d1x1: one decoder step of the segmentation head (models/heads/seg_head.py:63-67), nearest upsample + concat + conv1d_1x1 without the upsampled
-and the concatenated tensor (cbl_up_conv_*, csrc/up_conv.hip)."""
+and the concatenated tensor (cbl_up_conv_*, csrc/up_conv.hip).
+pool_bn / PoolBN: the batch norm + activation behind every local aggregation (local_aggregation_operators.py:232-238: scope 'pool_bn'), on rows that are an
+input and not a product (cbl_pool_bn_*, csrc/pool_bn.hip)."""
 import ctypes
 
 import torch
@@ -155,6 +157,108 @@ class Conv1d1x1(torch.nn.Module):
     def forward(self, features, shortcut=None):
         return conv1d_1x1(features, self.weights, self.biases, self.gamma, self.beta, self.moving_mean, self.moving_variance, is_training=self.training,
                           activation_fn=self.activation_fn, bn_momentum=self.bn_momentum, bn_eps=self.bn_eps, shortcut=shortcut)
+
+
+# ---------------------------------------------------------------------------------------------- the batch norm behind a local aggregation
+class _PoolBN(Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, moving, bn_mode, act, momentum, eps):
+        # (moving: as in _Conv1d1x1)
+        moving_mean, moving_variance = moving
+        L = _lib.lib()
+        rows, C = x.shape
+        dev = x.device
+        out = torch.empty_like(x)
+        save_mean, save_invstd = (torch.empty(C, dtype=torch.float32, device=dev) for _ in range(2)) if bn_mode else (None, None)
+        ws = _pool_bn_workspace(L, rows, C, dev) if bn_mode == 1 else None
+        _lib.check(L.cbl_pool_bn_forward(_ll(rows), _i(C), _lib.ptr(x), _i(bn_mode), _lib.ptr(gamma), _lib.ptr(beta), _f(eps), _f(momentum),
+                                         _lib.ptr(moving_mean), _lib.ptr(moving_variance), _i(act), _lib.ptr(save_mean), _lib.ptr(save_invstd), _lib.ptr(out),
+                                         _lib.ptr(ws), ctypes.c_size_t(ws.numel() if ws is not None else 0), _lib.stream_of(x)), "cbl_pool_bn_forward")
+        ctx.save_for_backward(x, gamma, save_mean, save_invstd, out)
+        ctx.cfg = (bn_mode, act)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, gamma, save_mean, save_invstd, out = ctx.saved_tensors
+        bn_mode, act = ctx.cfg
+        L = _lib.lib()
+        rows, C = x.shape
+        dev = x.device
+        grad_out = grad_out.contiguous()
+        need = ctx.needs_input_grad
+        gx = torch.empty_like(x) if need[0] else None
+        gg = torch.empty(C, dtype=torch.float32, device=dev) if bn_mode and need[1] else None
+        gbeta = torch.empty(C, dtype=torch.float32, device=dev) if bn_mode and need[2] else None
+        if rows == 0:
+            for g in (gg, gbeta):
+                if g is not None:
+                    g.zero_()
+            return (gx, gg, gbeta) + (None,) * 5
+        ws = _pool_bn_workspace(L, rows, C, dev) if bn_mode else None
+        _lib.check(L.cbl_pool_bn_backward(_ll(rows), _i(C), _lib.ptr(x), _i(bn_mode), _lib.ptr(gamma), _lib.ptr(save_mean), _lib.ptr(save_invstd), _i(act),
+                                          _lib.ptr(out), _lib.ptr(grad_out), _lib.ptr(gx), _lib.ptr(gg), _lib.ptr(gbeta), _lib.ptr(ws),
+                                          ctypes.c_size_t(ws.numel() if ws is not None else 0), _lib.stream_of(x)), "cbl_pool_bn_backward")
+        return (gx, gg, gbeta) + (None,) * 5
+
+
+def _pool_bn_workspace(L, rows, C, dev):
+    return torch.empty(max(L.cbl_pool_bn_workspace_bytes(_ll(rows), _i(C)), 1), dtype=torch.uint8, device=dev)
+
+
+def pool_bn(x, gamma=None, beta=None, moving_mean=None, moving_variance=None, *, is_training=True, activation_fn="relu", bn_momentum=0.98, bn_eps=1e-3):
+    """act(bn(x))  (rows, C): the batch norm and activation behind every local aggregation (local_aggregation_operators.py:232-238, :304-310, :482-488,
+    :730-736; batch_norm(..., scope='pool_bn') = tf.layers.batch_normalization) — cbl_pool_bn_* (csrc/pool_bn.hip) under autograd.  gamma /
+    beta: the batch norm (gamma None: bn=False, the activation alone); moving_mean / moving_variance: updated in place when training (TF convention), used
+    when not.  Runs on the current stream of the tensors' device; 1 <= C <= 4096.  There is no fallback: CPU tensors raise."""
+    _chk(x, "x")
+    for t, name in ((gamma, "gamma"), (beta, "beta"), (moving_mean, "moving_mean"), (moving_variance, "moving_variance")):
+        if t is not None:
+            _chk(t, name)
+    if x.dim() != 2:
+        raise ValueError("pool_bn: x of shape {}, (rows, C) expected".format(tuple(x.shape)))
+    C = x.shape[1]
+    if not 1 <= C <= MAX_WIDTH:
+        raise NotImplementedError("pool_bn: width {} (1 to {})".format(C, MAX_WIDTH))
+    if (gamma is None) != (beta is None):
+        raise ValueError("pool_bn: gamma and beta come together (both None: bn=False)")
+    if gamma is None and (moving_mean is not None or moving_variance is not None):
+        raise ValueError("pool_bn: moving statistics without a batch norm")
+    if (moving_mean is None) != (moving_variance is None):
+        raise ValueError("pool_bn: moving_mean and moving_variance come together")
+    if gamma is not None and not is_training and moving_mean is None:
+        raise ValueError("pool_bn: is_training=False needs moving_mean and moving_variance")
+    for t, name in ((gamma, "gamma"), (beta, "beta"), (moving_mean, "moving_mean"), (moving_variance, "moving_variance")):
+        if t is not None and tuple(t.shape) != (C,):
+            raise ValueError("pool_bn: {} of shape {}, ({},) expected".format(name, tuple(t.shape), C))
+    bn_mode = 0 if gamma is None else (1 if is_training else 2)
+    return _PoolBN.apply(x, gamma, beta, (moving_mean, moving_variance), bn_mode, _ACTIVATIONS.get(activation_fn, 0), float(bn_momentum), float(bn_eps))
+
+
+class PoolBN(torch.nn.Module):
+    """pool_bn with the reference's variables (TF names) under its scope ('pool_bn'; PseudoGrid's is 'bn'): `gamma` (ones), `beta` (zeros) and the buffers
+    `moving_mean` (zeros) / `moving_variance` (ones); bn=False: no variable at all, the activation alone"""
+
+    def __init__(self, fdim, activation_fn="relu", bn=True, bn_momentum=0.98, bn_eps=1e-3, scope="pool_bn"):
+        super().__init__()
+        if not 1 <= fdim <= MAX_WIDTH:
+            raise NotImplementedError("PoolBN: width {} (1 to {})".format(fdim, MAX_WIDTH))
+        self.activation_fn, self.bn_momentum, self.bn_eps, self.scope = activation_fn, bn_momentum, bn_eps, scope
+        if bn:
+            self.gamma = torch.nn.Parameter(torch.ones(fdim))
+            self.beta = torch.nn.Parameter(torch.zeros(fdim))
+            self.register_buffer("moving_mean", torch.zeros(fdim))
+            self.register_buffer("moving_variance", torch.ones(fdim))
+        else:
+            self.gamma = self.beta = self.moving_mean = self.moving_variance = None
+
+    def tf_scopes(self):
+        """variable name -> its TF variable scope: all four under the layer's name (tf.layers.batch_normalization(name=scope))"""
+        return {} if self.gamma is None else dict(gamma=self.scope, beta=self.scope, moving_mean=self.scope, moving_variance=self.scope)
+
+    def forward(self, x):
+        return pool_bn(x, self.gamma, self.beta, self.moving_mean, self.moving_variance, is_training=self.training, activation_fn=self.activation_fn,
+                       bn_momentum=self.bn_momentum, bn_eps=self.bn_eps)
 
 
 # ---------------------------------------------------------------------------------------------- the segmentation head's decoder step (DESIGN.md 6.14)

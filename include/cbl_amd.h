@@ -647,6 +647,32 @@ int cbl_up_conv_backward(long long n2, long long n1, int c_up, int c_skip, int c
                          float* grad_coarse, float* grad_skip, float* grad_weights, float* grad_biases, float* grad_gamma, float* grad_beta,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* a15  pool_bn  the batch norm + activation behind every local aggregation of the ConvNet, tensorflow/models/local_aggregation_operators.py:232-249,
+ *   :304-311, :482-500, :730-745 (batch_norm(..., scope='pool_bn') = tf.layers.batch_normalization, then relu / leaky_relu(0.2)): for x (rows,C)
+ *       out = act(bn(x))
+ *   bn_mode, activation, gamma / beta, eps, momentum, moving_mean / moving_var (both or neither under bn_mode 1, both under bn_mode 2) and save_mean /
+ *   save_invstd (C) are those of cbl_unary_layer_forward: bn_mode 0 none (out = act(x)) | 1 batch statistics over all rows, biased variance, moving =
+ *   moving * momentum + batch * (1 - momentum) | 2 moving statistics (no buffer is written); activation 0 none | 1 relu | 2 leaky_relu(0.2).
+ *   Any rows >= 0 (0: a no-op that leaves the moving statistics alone; 1: variance 0), 1 <= C <= 4096 (wider: CBL_ERR_UNSUPPORTED, and a workspace size of
+ *   0).  No alignment is required beyond a float's: a width that is no multiple of 4 or a base that is not 16-byte aligned takes scalar loads.  Bad
+ *   arguments return CBL_ERR_BAD_ARG before any launch, a short workspace CBL_ERR_WORKSPACE (one size for both calls; needed by the forward call under
+ *   bn_mode 1 and by the backward call under bn_mode 1 and 2).
+ *   The statistics are centred at every level (a thread's rows about its first row, the threads and the workgroups combined in fp64 in a fixed order):
+ *   there is no sum of x^2.  Up to 512 rows a call is ONE launch; more rows: a statistics (sums) pass, a finalize and an element pass, 12 rows C bytes
+ *   forward and 28 rows C bytes backward.  The rule depends on rows alone.  No float atomics: every output is stored once in a fixed summation order
+ *   (two calls give the same bits); no allocation or synchronisation inside a call. */
+size_t cbl_pool_bn_workspace_bytes(long long rows, int C);
+int cbl_pool_bn_forward(long long rows, int C, const float* x, int bn_mode, const float* gamma, const float* beta, float eps, float momentum,
+                        float* moving_mean, float* moving_var, int activation, float* save_mean, float* save_invstd, float* out,
+                        void* workspace, size_t workspace_bytes, void* stream);
+/* gradients (any may be NULL), all WRITTEN: with dz = grad_out * act'(out) (the mask is out > 0; out may be NULL with activation 0) and xhat = (x - mean) *
+ * invstd:  grad_x (rows,C) = gamma * invstd * (dz - sum dz / N - xhat * sum(dz * xhat) / N), N = rows (bn_mode 1) | gamma * invstd * dz (bn_mode 2) | dz
+ * (bn_mode 0);  grad_gamma = sum dz * xhat, grad_beta = sum dz (C; bn_mode 1 and 2 — given under bn_mode 0: CBL_ERR_BAD_ARG).  save_mean / save_invstd:
+ * as the forward call left them. */
+int cbl_pool_bn_backward(long long rows, int C, const float* x, int bn_mode, const float* gamma, const float* save_mean, const float* save_invstd,
+                         int activation, const float* out, const float* grad_out, float* grad_x, float* grad_gamma, float* grad_beta,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* a4  PointTransformerLayer pytorch/model/blocks.py:31-44, the C-wide part without its (n,K,C) tensors (C = 32 or 64, G = C/8):
  *   p1 (n,K,3) = ReLU(BN(Linear(3,3)(p_j - p_i)))  [computed by the caller: narrow],  p_r = Linear(3,C)(p1) = p1 @ W3C^T + b3C  [never stored]
  * attn_w2:  w2 (n,K,G) = Linear(C,G)( ReLU( BN_C( x_k[idx] - x_q + p_r ) ) )       (:39 and the first half of linear_w, :25-27)
