@@ -41,7 +41,7 @@ class _KPConvWeights(torch.nn.Module):
         if init == "xavier":
             torch.nn.init.xavier_uniform_(self.weights)
         elif init == "fan_in":
-            LA._fan_in_init_(self.weights)
+            LA.fan_in_init_(self.weights)
         else:
             raise NotImplementedError("pseudo_grid: init {} ('xavier' or 'fan_in')".format(init))
 

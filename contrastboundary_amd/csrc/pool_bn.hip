@@ -1,8 +1,8 @@
 // a15  The batch norm + activation that follows every local aggregation of the ConvNet (tensorflow/models/local_aggregation_operators.py:232-249, :304-311,
 //      :482-500, :730-745: batch_norm(..., scope='pool_bn') = tf.layers.batch_normalization, then relu / leaky_relu(0.2)): for x (rows, C)
 //     out = act(bn(x))
-// forward and backward, any 1 <= C <= 4096 and any number of rows.  The conventions (bn_mode, activation, the mask out > 0, the gradient
-// formulae, error codes) are those of the unary entries (unary_layer.hip); what differs is that x is an INPUT here and not the product of a launch.
+// forward and backward, any 1 <= C <= 4096 and any number of rows.  The batch norm's conventions, its argument checks and the kernels that
+// are the unary entries' too come from tf_bn.h; what is here is the statistics scheme and the element passes of rows that are an INPUT, not a product.
 //   threads  : a thread owns one group of four columns (one 16-byte load a row) and every nrl-th row of its workgroup's rows: a workgroup covers a slab of
 //              w <= 64 column groups with nrl = 256 / w row lanes (thread = row lane * w + column group), so a narrow C still fills the workgroup: C = 72 is
 //              18 groups x 14 row lanes.  A thread fetches 8 rows at a time (eight independent 16-byte loads in flight).  Widths that are no multiple of 4
@@ -17,7 +17,7 @@
 //              statistics, finalize, element pass (12 rows C bytes), backward = sums (reads grad_out, out, x), finalize, element pass (reads the three, writes
 //              grad_x): 28 rows C bytes.  The rule depends on rows alone.
 // No float atomics; every output is stored once in a fixed summation order (the grids depend on the shapes alone); no allocation or synchronisation.
-#include "pair_tile.h"                                            // pair_act / pair_dact (the activation's encoding), pair_f32x4, pair_up256
+#include "tf_bn.h"                                                // and through it pair_tile.h: pair_act / pair_dact, pair_f32x4, pair_up256
 
 namespace {
 
@@ -37,24 +37,6 @@ inline PbGeom pb_geom(int C, int max_w)
     g.nrl = PB_BLOCK / g.w;
     return g;
 }
-
-__device__ __forceinline__ pair_f32x4 pb_ld4(const float* __restrict__ p, bool vec, int nv)
-{
-    if (vec) return *reinterpret_cast<const pair_f32x4*>(p);
-    pair_f32x4 t = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int q = 0; q < 4; q++) if (q < nv) t[q] = p[q];
-    return t;
-}
-__device__ __forceinline__ void pb_st4(float* __restrict__ p, pair_f32x4 v, bool vec, int nv)
-{
-    if (vec) { *reinterpret_cast<pair_f32x4*>(p) = v; return; }
-#pragma unroll
-    for (int q = 0; q < 4; q++) if (q < nv) p[q] = v[q];
-}
-
-// the one association of the batch norm (forward and the xhat of the backward passes agree), as ul_xhat / ul_z
-__device__ __forceinline__ float pb_xhat(float x, float mean, float invstd) { return (x - mean) * invstd; }
 
 // this thread's place: column group cg of the slab blockIdx.y, row lane rl (active: rl < nrl and the group exists)
 struct PbThread { int rl, c, nv; bool on; };
@@ -80,7 +62,7 @@ __device__ __forceinline__ void pb_rows(const float* __restrict__ x, int C, bool
         for (int j = 0; j < PB_BATCH; j++) {
             const long long rr = r + (long long)j * nrl;
             v[j] = pair_f32x4{0.f, 0.f, 0.f, 0.f};
-            if (rr < r1) { v[j] = pb_ld4(x + (size_t)rr * C + t.c, vec, t.nv); cnt = j + 1; }
+            if (rr < r1) { v[j] = tfbn_ld4(x + (size_t)rr * C + t.c, vec, t.nv); cnt = j + 1; }
         }
         f(v, cnt);
     }
@@ -176,26 +158,13 @@ __device__ __forceinline__ void pb_normalize_rows(const PbForward& a, const PbTh
             if (j >= cnt) continue;
             pair_f32x4 o;
 #pragma unroll
-            for (int q = 0; q < 4; q++) o[q] = pair_act(a.act, a.bn_mode ? pb_xhat(v[j][q], mean[q], invstd[q]) * g[q] + b[q] : v[j][q]);
-            pb_st4(a.out + (size_t)(r + (long long)j * a.nrl) * a.C + t.c, o, a.vec != 0, t.nv);
+            for (int q = 0; q < 4; q++) o[q] = pair_act(a.act, a.bn_mode ? tfbn_xhat(v[j][q], mean[q], invstd[q]) * g[q] + b[q] : v[j][q]);
+            tfbn_st4(a.out + (size_t)(r + (long long)j * a.nrl) * a.C + t.c, o, a.vec != 0, t.nv);
         }
         r += (long long)PB_BATCH * a.nrl;
     });
 }
 
-// what the statistics of a column become: save_mean / save_invstd, the moving statistics the TF way (biased variance)
-__device__ __forceinline__ void pb_finish_stats(const PbForward& a, int c, double N, double mean, double m2, float& fm, float& fi)
-{
-    const double var = m2 / N;                                      // biased (tf.nn.moments)
-    const float fv = (float)var;
-    fm = (float)mean;
-    fi = (float)(1.0 / sqrt(var + (double)a.eps));
-    a.save_mean[c] = fm;
-    a.save_invstd[c] = fi;
-    if (a.moving_mean) a.moving_mean[c] = a.moving_mean[c] * a.momentum + fm * (1.f - a.momentum);
-    if (a.moving_var) a.moving_var[c] = a.moving_var[c] * a.momentum + fv * (1.f - a.momentum);
-}
-__device__ __forceinline__ float pb_moving_invstd(float var, float eps) { return (float)(1.0 / sqrt((double)var + (double)eps)); }
 
 // the single launch: grid (1, slabs); every bn_mode
 __global__ __launch_bounds__(PB_BLOCK) void pb_forward_small_kernel(PbForward a)
@@ -215,11 +184,11 @@ __global__ __launch_bounds__(PB_BLOCK) void pb_forward_small_kernel(PbForward a)
         if (colthread) {
             double dm, dq;
             const double N = pb_combine_stats(S, a.w, a.nrl, j, dm, dq);
-            pb_finish_stats(a, c, N, dm, dq, S.col[0][j], S.col[1][j]);
+            tfbn_finish_stats(c, N, dm, dq, a.eps, a.momentum, a.moving_mean, a.moving_var, a.save_mean, a.save_invstd, S.col[0][j], S.col[1][j]);
         }
     } else if (a.bn_mode == 2 && colthread) {
         a.save_mean[c] = S.col[0][j] = a.moving_mean[c];
-        a.save_invstd[c] = S.col[1][j] = pb_moving_invstd(a.moving_var[c], a.eps);
+        a.save_invstd[c] = S.col[1][j] = tfbn_moving_invstd(a.moving_var[c], a.eps);
     }
     __syncthreads();
     pair_f32x4 mean = {0.f, 0.f, 0.f, 0.f}, invstd = {1.f, 1.f, 1.f, 1.f};
@@ -286,18 +255,8 @@ __global__ __launch_bounds__(PB_BLOCK) void pb_stats_finalize_kernel(PbForward a
         double tot = 0.0;
         for (int i = 0; i < 8; i++) tot += red[i][cl];
         float fm, fi;
-        pb_finish_stats(a, c, (double)a.rows, mean, tot, fm, fi);
+        tfbn_finish_stats(c, (double)a.rows, mean, tot, a.eps, a.momentum, a.moving_mean, a.moving_var, a.save_mean, a.save_invstd, fm, fi);
     }
-}
-
-// bn_mode 2, chunked: the statistics used are the moving ones
-__global__ __launch_bounds__(PB_BLOCK) void pb_moving_stats_kernel(int C, const float* __restrict__ moving_mean, const float* __restrict__ moving_var, float eps,
-                                                                    float* __restrict__ save_mean, float* __restrict__ save_invstd)
-{
-    const int c = blockIdx.x * PB_BLOCK + threadIdx.x;
-    if (c >= C) return;
-    save_mean[c] = moving_mean[c];
-    save_invstd[c] = pb_moving_invstd(moving_var[c], eps);
 }
 
 // chunked, the element pass: grid (chunks, slabs)
@@ -331,9 +290,9 @@ __device__ __forceinline__ void pb_backward_rows(const PbBackward& a, const PbTh
         const bool two = rb < r1;
         const size_t oa = (size_t)r * a.C + t.c, ob = (size_t)rb * a.C + t.c;
         const pair_f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-        pair_f32x4 ga = pb_ld4(a.go + oa, vec, t.nv), gb = two ? pb_ld4(a.go + ob, vec, t.nv) : zero;
-        const pair_f32x4 ha = a.act ? pb_ld4(a.out + oa, vec, t.nv) : zero, hb = (a.act && two) ? pb_ld4(a.out + ob, vec, t.nv) : zero;
-        const pair_f32x4 xa = need_x ? pb_ld4(a.x + oa, vec, t.nv) : zero, xb = (need_x && two) ? pb_ld4(a.x + ob, vec, t.nv) : zero;
+        pair_f32x4 ga = tfbn_ld4(a.go + oa, vec, t.nv), gb = two ? tfbn_ld4(a.go + ob, vec, t.nv) : zero;
+        const pair_f32x4 ha = a.act ? tfbn_ld4(a.out + oa, vec, t.nv) : zero, hb = (a.act && two) ? tfbn_ld4(a.out + ob, vec, t.nv) : zero;
+        const pair_f32x4 xa = need_x ? tfbn_ld4(a.x + oa, vec, t.nv) : zero, xb = (need_x && two) ? tfbn_ld4(a.x + ob, vec, t.nv) : zero;
         if (a.act)
 #pragma unroll
             for (int q = 0; q < 4; q++) { ga[q] = ga[q] * pair_dact(a.act, ha[q]); gb[q] = gb[q] * pair_dact(a.act, hb[q]); }
@@ -353,7 +312,7 @@ __device__ __forceinline__ void pb_thread_sums(const PbBackward& a, const PbThre
     for (int q = 0; q < 4; q++) if (q < t.nv) { mean[q] = a.mean[t.c + q]; invstd[q] = a.invstd[t.c + q]; }
     pb_backward_rows(a, t, true, r0, r1, [&](long long, const pair_f32x4& dz, const pair_f32x4& x) {
 #pragma unroll
-        for (int q = 0; q < 4; q++) { s1[q] += (double)dz[q]; s2[q] += (double)(dz[q] * pb_xhat(x[q], mean[q], invstd[q])); }
+        for (int q = 0; q < 4; q++) { s1[q] += (double)dz[q]; s2[q] += (double)(dz[q] * tfbn_xhat(x[q], mean[q], invstd[q])); }
     });
 }
 
@@ -369,8 +328,8 @@ __device__ __forceinline__ void pb_dx_rows(const PbBackward& a, const PbThread& 
         pair_f32x4 dx;
 #pragma unroll
         for (int q = 0; q < 4; q++)
-            dx[q] = a.bn_mode == 1 ? gi[q] * ((dz[q] - s1n[q]) - pb_xhat(x[q], mean[q], invstd[q]) * s2n[q]) : a.bn_mode == 2 ? gi[q] * dz[q] : dz[q];
-        pb_st4(a.gx + (size_t)row * a.C + t.c, dx, a.vec != 0, t.nv);
+            dx[q] = a.bn_mode == 1 ? gi[q] * ((dz[q] - s1n[q]) - tfbn_xhat(x[q], mean[q], invstd[q]) * s2n[q]) : a.bn_mode == 2 ? gi[q] * dz[q] : dz[q];
+        tfbn_st4(a.gx + (size_t)row * a.C + t.c, dx, a.vec != 0, t.nv);
     });
 }
 
@@ -430,19 +389,7 @@ __global__ __launch_bounds__(PB_BLOCK) void pb_sums_kernel(PbBackward a)
         pb_combine_sums(S, a.w, a.nrl, j, dst[0], dst[1]);
     }
 }
-// the chunks' sums in chunk order: grad_beta, grad_gamma and the two values the element pass reads
-__global__ __launch_bounds__(PB_BLOCK) void pb_sums_finalize_kernel(int C, int nchunks, const double* __restrict__ part, float* __restrict__ sums,
-                                                                     float* __restrict__ grad_beta, float* __restrict__ grad_gamma)
-{
-    const int c = blockIdx.x * PB_BLOCK + threadIdx.x;
-    if (c >= C) return;
-    double s1 = 0.0, s2 = 0.0;
-#pragma unroll 4
-    for (int k = 0; k < nchunks; k++) { s1 += part[((size_t)k * C + c) * 2]; s2 += part[((size_t)k * C + c) * 2 + 1]; }
-    sums[c] = (float)s1; sums[C + c] = (float)s2;
-    if (grad_beta) grad_beta[c] = (float)s1;
-    if (grad_gamma) grad_gamma[c] = (float)s2;
-}
+// (the chunks' sums in chunk order — grad_beta, grad_gamma and the two values the element pass reads —: tfbn_sums_finalize_kernel)
 
 // chunked, the element pass: grid (chunks, slabs)
 __global__ __launch_bounds__(PB_BLOCK) void pb_dx_kernel(PbBackward a)
@@ -487,11 +434,6 @@ inline PbPlan pb_plan(long long rows, int C)
     p.bytes = o + 256;                                              // the base is rounded up to 256 bytes
     return p;
 }
-inline char* pb_base(void* ws) { return reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255); }
-inline bool pb_vec(int C, const void* p0, const void* p1 = nullptr, const void* p2 = nullptr, const void* p3 = nullptr)
-{
-    return C % 4 == 0 && cbl_host_aligned16(p0) && cbl_host_aligned16(p1) && cbl_host_aligned16(p2) && cbl_host_aligned16(p3);
-}
 
 }  // namespace
 
@@ -505,21 +447,19 @@ CBL_EXPORT int cbl_pool_bn_forward(long long rows, int C, const float* x, int bn
                                    float* moving_mean, float* moving_var, int activation, float* save_mean, float* save_invstd, float* out, void* workspace,
                                    size_t workspace_bytes, void* stream)
 {
-    if (rows < 0 || C < 1 || bn_mode < 0 || bn_mode > 2 || activation < 0 || activation > 2) return CBL_ERR_BAD_ARG;
+    if (rows < 0 || C < 1 || !tfbn_modes_ok(bn_mode, activation)) return CBL_ERR_BAD_ARG;
     if (C > PB_MAX_C) return CBL_ERR_UNSUPPORTED;
     if (rows == 0) return CBL_OK;
     if (!x || !out) return CBL_ERR_BAD_ARG;
-    if (bn_mode != 0 && (!gamma || !beta || !save_mean || !save_invstd || !(eps > 0.f))) return CBL_ERR_BAD_ARG;
-    if (bn_mode == 2 && (!moving_mean || !moving_var)) return CBL_ERR_BAD_ARG;
-    if (bn_mode == 1 && ((moving_mean == nullptr) != (moving_var == nullptr))) return CBL_ERR_BAD_ARG;
+    if (const int rc = tfbn_check_forward(bn_mode, gamma, beta, eps, moving_mean, moving_var, save_mean, save_invstd)) return rc;
     const PbPlan p = pb_plan(rows, C);
     if (bn_mode == 1 && (!workspace || workspace_bytes < p.bytes)) return CBL_ERR_WORKSPACE;
     hipStream_t st = cbl_stream(stream);
     PbForward a;
-    a.rows = rows; a.chunk_rows = p.chunk_rows; a.C = C; a.ncg = p.g.ncg; a.w = p.g.w; a.nrl = p.g.nrl; a.vec = pb_vec(C, x, out);
+    a.rows = rows; a.chunk_rows = p.chunk_rows; a.C = C; a.ncg = p.g.ncg; a.w = p.g.w; a.nrl = p.g.nrl; a.vec = tfbn_vec(C, x, out);
     a.bn_mode = bn_mode; a.act = activation; a.eps = eps; a.momentum = momentum;
     a.x = x; a.gamma = gamma; a.beta = beta; a.moving_mean = moving_mean; a.moving_var = moving_var; a.save_mean = save_mean; a.save_invstd = save_invstd;
-    a.out = out; a.part = bn_mode == 1 ? reinterpret_cast<float*>(pb_base(workspace) + p.off_part) : nullptr;
+    a.out = out; a.part = bn_mode == 1 ? reinterpret_cast<float*>(tfbn_base(workspace) + p.off_part) : nullptr;
     if (p.small) {
         hipLaunchKernelGGL(pb_forward_small_kernel, dim3(1, p.g.slabs), dim3(PB_BLOCK), 0, st, a);
         return cbl_status();
@@ -529,7 +469,7 @@ CBL_EXPORT int cbl_pool_bn_forward(long long rows, int C, const float* x, int bn
         hipLaunchKernelGGL(pb_stats_kernel, grid, dim3(PB_BLOCK), 0, st, a);
         hipLaunchKernelGGL(pb_stats_finalize_kernel, dim3(cbl_div_up(C, 32)), dim3(PB_BLOCK), 0, st, a, p.nchunks);
     } else if (bn_mode == 2)
-        hipLaunchKernelGGL(pb_moving_stats_kernel, dim3(cbl_div_up(C, PB_BLOCK)), dim3(PB_BLOCK), 0, st, C, moving_mean, moving_var, eps, save_mean, save_invstd);
+        tfbn_launch_moving_stats(st, C, moving_mean, moving_var, eps, save_mean, save_invstd);
     hipLaunchKernelGGL(pb_normalize_kernel, grid, dim3(PB_BLOCK), 0, st, a);
     return cbl_status();
 }
@@ -538,19 +478,17 @@ CBL_EXPORT int cbl_pool_bn_backward(long long rows, int C, const float* x, int b
                                     int activation, const float* out, const float* grad_out, float* grad_x, float* grad_gamma, float* grad_beta,
                                     void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (rows < 0 || C < 1 || bn_mode < 0 || bn_mode > 2 || activation < 0 || activation > 2) return CBL_ERR_BAD_ARG;
+    if (rows < 0 || C < 1 || !tfbn_modes_ok(bn_mode, activation)) return CBL_ERR_BAD_ARG;
     if (C > PB_MAX_C) return CBL_ERR_UNSUPPORTED;
     if (rows == 0) return CBL_OK;
-    if (!grad_out) return CBL_ERR_BAD_ARG;
-    if (activation != 0 && !out) return CBL_ERR_BAD_ARG;
-    if (bn_mode != 0 && (!x || !gamma || !save_mean || !save_invstd)) return CBL_ERR_BAD_ARG;
-    if (bn_mode == 0 && (grad_gamma || grad_beta)) return CBL_ERR_BAD_ARG;
+    if (!grad_out || (bn_mode != 0 && !x)) return CBL_ERR_BAD_ARG;
+    if (const int rc = tfbn_check_backward(bn_mode, activation, gamma, save_mean, save_invstd, out, grad_gamma, grad_beta)) return rc;
     const PbPlan p = pb_plan(rows, C);
     if (bn_mode != 0 && (!workspace || workspace_bytes < p.bytes)) return CBL_ERR_WORKSPACE;
     hipStream_t st = cbl_stream(stream);
-    char* base = bn_mode != 0 ? pb_base(workspace) : nullptr;
+    char* base = bn_mode != 0 ? tfbn_base(workspace) : nullptr;
     PbBackward a;
-    a.rows = rows; a.chunk_rows = p.chunk_rows; a.C = C; a.ncg = p.g.ncg; a.w = p.g.w; a.nrl = p.g.nrl; a.vec = pb_vec(C, x, out, grad_out, grad_x);
+    a.rows = rows; a.chunk_rows = p.chunk_rows; a.C = C; a.ncg = p.g.ncg; a.w = p.g.w; a.nrl = p.g.nrl; a.vec = tfbn_vec(C, x, out, grad_out, grad_x);
     a.bn_mode = bn_mode; a.act = activation; a.inv_n = (float)(1.0 / (double)rows);
     a.want_sums = bn_mode == 1 ? (grad_x || grad_gamma || grad_beta) : bn_mode == 2 ? (grad_gamma || grad_beta) : 0;
     a.x = x; a.gamma = gamma; a.mean = save_mean; a.invstd = save_invstd; a.out = out; a.go = grad_out;
@@ -565,8 +503,7 @@ CBL_EXPORT int cbl_pool_bn_backward(long long rows, int C, const float* x, int b
     const dim3 grid(p.nchunks, p.g.slabs);
     if (a.want_sums) {
         hipLaunchKernelGGL(pb_sums_kernel, grid, dim3(PB_BLOCK), 0, st, a);
-        hipLaunchKernelGGL(pb_sums_finalize_kernel, dim3(cbl_div_up(C, PB_BLOCK)), dim3(PB_BLOCK), 0, st, C, p.nchunks, a.part, const_cast<float*>(a.sums), grad_beta,
-                           grad_gamma);
+        tfbn_launch_sums_finalize(st, C, p.nchunks, a.part, const_cast<float*>(a.sums), grad_beta, grad_gamma);
     }
     if (grad_x) hipLaunchKernelGGL(pb_dx_kernel, grid, dim3(PB_BLOCK), 0, st, a);
     return cbl_status();

@@ -33,39 +33,27 @@ CBL_EXPORT int cbl_unary_layer_forward(long long rows, int c_in, int c_out, cons
                                        int activation, float* save_mean, float* save_invstd, float* y, float* out, void* workspace, size_t workspace_bytes,
                                        void* stream)
 {
-    if (rows < 0 || c_in < 1 || c_out < 1 || bn_mode < 0 || bn_mode > 2 || activation < 0 || activation > 2) return CBL_ERR_BAD_ARG;
+    if (rows < 0 || c_in < 1 || c_out < 1 || !tfbn_modes_ok(bn_mode, activation)) return CBL_ERR_BAD_ARG;
     if (!ul_dims_ok(c_in, c_out)) return CBL_ERR_UNSUPPORTED;
     if (rows == 0) return CBL_OK;
-    if (!x || !weights || !out) return CBL_ERR_BAD_ARG;
-    if (bn_mode != 0 && (!gamma || !beta || !save_mean || !save_invstd || !y || !(eps > 0.f))) return CBL_ERR_BAD_ARG;
-    if (bn_mode == 2 && (!moving_mean || !moving_var)) return CBL_ERR_BAD_ARG;
-    if (bn_mode == 1 && ((moving_mean == nullptr) != (moving_var == nullptr))) return CBL_ERR_BAD_ARG;
+    if (!x || !weights || !out || (bn_mode != 0 && !y)) return CBL_ERR_BAD_ARG;
+    if (const int rc = tfbn_check_forward(bn_mode, gamma, beta, eps, moving_mean, moving_var, save_mean, save_invstd)) return rc;
     const UlPlan p = ul_plan(rows, c_in, c_out);
     if (bn_mode == 1 && (!workspace || workspace_bytes < p.bytes)) return CBL_ERR_WORKSPACE;
     hipStream_t st = cbl_stream(stream);
-    char* base = ul_base(workspace);
-    if (bn_mode == 2)
-        hipLaunchKernelGGL(ul_moving_stats_kernel, dim3(cbl_div_up(c_out, UL_BLOCK)), dim3(UL_BLOCK), 0, st, c_out, moving_mean, moving_var, eps, save_mean, save_invstd);
+    char* base = tfbn_base(workspace);
+    if (bn_mode == 2) tfbn_launch_moving_stats(st, c_out, moving_mean, moving_var, eps, save_mean, save_invstd);
     UlForward f;
     f.rows = rows; f.row_tiles = p.row_tiles; f.cin = c_in; f.cout = c_out;
-    f.veca = ul_vec(c_in, x); f.vecb = ul_vec(c_out, weights);
+    f.veca = tfbn_vec(c_in, x); f.vecb = tfbn_vec(c_out, weights);
     f.fuse = bn_mode != 1; f.bn = bn_mode != 0; f.act = activation;
     f.x = x; f.w = weights; f.bias = biases; f.mean = save_mean; f.invstd = save_invstd; f.gamma = gamma; f.beta = beta; f.shortcut = shortcut;
     f.y = y; f.out = out; f.part = bn_mode == 1 ? reinterpret_cast<float*>(base + p.off_part) : nullptr;
     f.up_p = nullptr; f.up_idx = nullptr; f.up_n1 = 0; f.up_k = 0;
     const dim3 grid((unsigned)(p.row_tiles > UL_ROW_BLOCKS ? UL_ROW_BLOCKS : p.row_tiles), cbl_div_up(c_out, UL_T));
     hipLaunchKernelGGL(ul_forward_kernel<false>, grid, dim3(UL_BLOCK), 0, st, f);
-    if (bn_mode == 1) {
-        hipLaunchKernelGGL(ul_stats_finalize_kernel, dim3(cbl_div_up(c_out, 32)), dim3(UL_BLOCK), 0, st, rows, c_out, p.row_tiles, f.part, eps, momentum, moving_mean,
-                           moving_var, save_mean, save_invstd);
-        UlWalk a = {};
-        a.rows = rows; a.cout = c_out; a.act = activation; a.bn_mode = 1;
-        a.vec = ul_vec(c_out, y, out, shortcut);
-        a.y = y; a.mean = save_mean; a.invstd = save_invstd; a.gamma = gamma; a.beta = beta; a.shortcut = shortcut; a.out = out;
-        unsigned g;
-        ul_walk_shape(a, &g);
-        hipLaunchKernelGGL(ul_normalize_kernel, dim3(g), dim3(UL_BLOCK), 0, st, a);
-    }
+    if (bn_mode == 1)
+        ul_launch_bn_tail(st, rows, c_out, p.row_tiles, f.part, eps, momentum, moving_mean, moving_var, save_mean, save_invstd, gamma, beta, activation, y, shortcut, out);
     return cbl_status();
 }
 
@@ -74,17 +62,15 @@ CBL_EXPORT int cbl_unary_layer_backward(long long rows, int c_in, int c_out, con
                                         const float* grad_out, float* grad_x, float* grad_weights, float* grad_biases, float* grad_gamma, float* grad_beta,
                                         float* grad_shortcut, void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (rows < 0 || c_in < 1 || c_out < 1 || bn_mode < 0 || bn_mode > 2 || activation < 0 || activation > 2) return CBL_ERR_BAD_ARG;
+    if (rows < 0 || c_in < 1 || c_out < 1 || !tfbn_modes_ok(bn_mode, activation)) return CBL_ERR_BAD_ARG;
     if (!ul_dims_ok(c_in, c_out)) return CBL_ERR_UNSUPPORTED;
     if (rows == 0) return CBL_OK;
-    if (!x || !weights || !grad_out) return CBL_ERR_BAD_ARG;
-    if (activation != 0 && !out) return CBL_ERR_BAD_ARG;
-    if (bn_mode != 0 && (!gamma || !save_mean || !save_invstd || !y)) return CBL_ERR_BAD_ARG;
-    if (bn_mode == 0 && (grad_gamma || grad_beta)) return CBL_ERR_BAD_ARG;
+    if (!x || !weights || !grad_out || (bn_mode != 0 && !y)) return CBL_ERR_BAD_ARG;
+    if (const int rc = tfbn_check_backward(bn_mode, activation, gamma, save_mean, save_invstd, out, grad_gamma, grad_beta)) return rc;
     const UlPlan p = ul_plan(rows, c_in, c_out);
     if (!workspace || workspace_bytes < p.bytes) return CBL_ERR_WORKSPACE;
     hipStream_t st = cbl_stream(stream);
-    char* base = ul_base(workspace);
+    char* base = tfbn_base(workspace);
     float* sums = reinterpret_cast<float*>(base + p.off_sums);
     const bool products = grad_x || grad_weights || grad_biases;
     if (bn_mode == 1 ? (products || grad_gamma || grad_beta) : (grad_gamma || grad_beta)) {
@@ -94,16 +80,9 @@ CBL_EXPORT int cbl_unary_layer_backward(long long rows, int c_in, int c_out, con
     // dy: grad_out itself where neither a batch norm nor an activation stands between them
     const bool identity = bn_mode == 0 && activation == 0;
     const float* dy = identity ? grad_out : reinterpret_cast<float*>(base + p.off_dy);
-    if ((products && !identity) || grad_shortcut) {
-        UlWalk a = {};
-        a.rows = rows; a.cout = c_out; a.act = activation; a.bn_mode = bn_mode; a.inv_n = (float)(1.0 / (double)rows);
-        a.dy = (products && !identity) ? const_cast<float*>(dy) : nullptr;
-        a.vec = ul_vec(c_out, grad_out, out, y, a.dy, grad_shortcut);
-        a.go = grad_out; a.out_in = out; a.y = y; a.mean = save_mean; a.invstd = save_invstd; a.gamma = gamma; a.sums = sums; a.gs = grad_shortcut;
-        unsigned g;
-        ul_walk_shape(a, &g);
-        hipLaunchKernelGGL(ul_dy_kernel, dim3(g), dim3(UL_BLOCK), 0, st, a);
-    }
+    if ((products && !identity) || grad_shortcut)
+        ul_launch_dy(st, rows, c_out, bn_mode, activation, grad_out, out, y, save_mean, save_invstd, gamma, sums,
+                     (products && !identity) ? const_cast<float*>(dy) : nullptr, grad_shortcut);
     if (grad_x) ul_launch_dgrad(st, rows, c_in, c_out, dy, weights, grad_x);
     if (grad_weights || grad_biases)
         ul_launch_wgrad(st, p, rows, c_in, c_out, x, dy, grad_weights, grad_biases, reinterpret_cast<float*>(base + p.off_wpart));

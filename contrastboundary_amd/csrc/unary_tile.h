@@ -5,7 +5,7 @@
 #pragma once
 #include <cstdlib>
 
-#include "pair_tile.h"                                            // pair_act / pair_dact (the activation's encoding), pair_f32x4, pair_up256
+#include "tf_bn.h"                                                // the batch norm's conventions, its shared kernels and checks; pair_tile.h: pair_act / pair_dact, pair_f32x4, pair_up256
 
 namespace {
 
@@ -87,10 +87,9 @@ __device__ __forceinline__ void ul_tile_product(const float* __restrict__ A, lon
 }
 
 // z of one element: the batch norm in ONE association (forward epilogue, normalise pass and xhat of the backward passes agree), then the shortcut
-__device__ __forceinline__ float ul_xhat(float y, float mean, float invstd) { return (y - mean) * invstd; }
 __device__ __forceinline__ float ul_z(float y, bool bn, float mean, float invstd, float gamma, float beta, float sc)
 {
-    const float z = bn ? ul_xhat(y, mean, invstd) * gamma + beta : y;
+    const float z = bn ? tfbn_xhat(y, mean, invstd) * gamma + beta : y;
     return z + sc;
 }
 
@@ -211,6 +210,7 @@ __global__ __launch_bounds__(UL_BLOCK) void ul_stats_finalize_kernel(long long r
     if (g == 0 && ok) {
         double tot = 0.0;
         for (int j = 0; j < 8; j++) tot += red[j][cl];
+        // (tfbn_finish_stats' statements in this kernel's own order: written through that function the kernel compiles to another instruction order)
         const double var = tot / (double)rows;                     // biased (tf.nn.moments)
         const float fm = (float)mean, fv = (float)var;
         save_mean[c] = fm;
@@ -220,31 +220,7 @@ __global__ __launch_bounds__(UL_BLOCK) void ul_stats_finalize_kernel(long long r
     }
 }
 
-// bn_mode 2: the statistics used are the moving ones
-__global__ __launch_bounds__(UL_BLOCK) void ul_moving_stats_kernel(int cout, const float* __restrict__ moving_mean, const float* __restrict__ moving_var, float eps,
-                                                                    float* __restrict__ save_mean, float* __restrict__ save_invstd)
-{
-    const int c = blockIdx.x * UL_BLOCK + threadIdx.x;
-    if (c >= cout) return;
-    save_mean[c] = moving_mean[c];
-    save_invstd[c] = (float)(1.0 / sqrt((double)moving_var[c] + (double)eps));
-}
-
 // ---- elementwise passes: a thread per (row, group of four columns), trips of rb rows, workgroups walking the trips past the grid cap
-__device__ __forceinline__ pair_f32x4 ul_ld4(const float* __restrict__ p, bool vec, int nv)
-{
-    if (vec) return *reinterpret_cast<const pair_f32x4*>(p);
-    pair_f32x4 t = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int q = 0; q < 4; q++) if (q < nv) t[q] = p[q];
-    return t;
-}
-__device__ __forceinline__ void ul_st4(float* __restrict__ p, pair_f32x4 v, bool vec, int nv)
-{
-    if (vec) { *reinterpret_cast<pair_f32x4*>(p) = v; return; }
-#pragma unroll
-    for (int q = 0; q < 4; q++) if (q < nv) p[q] = v[q];
-}
 template <class F>
 __device__ __forceinline__ void ul_walk(long long rows, int ncg, int rb, CblFastDiv dv, F f)
 {
@@ -274,13 +250,13 @@ __global__ __launch_bounds__(UL_BLOCK) void ul_normalize_kernel(UlWalk a)
     ul_walk(a.rows, a.ncg, a.rb, a.dv, [&](long long row, int cg) {
         const int c = 4 * cg, nv = a.cout - c;
         const size_t o = (size_t)row * a.cout + c;
-        const pair_f32x4 y = ul_ld4(a.y + o, a.vec != 0, nv);
+        const pair_f32x4 y = tfbn_ld4(a.y + o, a.vec != 0, nv);
         pair_f32x4 sc = {0.f, 0.f, 0.f, 0.f}, r = {0.f, 0.f, 0.f, 0.f};
-        if (a.shortcut) sc = ul_ld4(a.shortcut + o, a.vec != 0, nv);
+        if (a.shortcut) sc = tfbn_ld4(a.shortcut + o, a.vec != 0, nv);
 #pragma unroll
         for (int q = 0; q < 4; q++)
             if (q < nv) r[q] = pair_act(a.act, ul_z(y[q], true, a.mean[c + q], a.invstd[c + q], a.gamma[c + q], a.beta[c + q], sc[q]));
-        ul_st4(a.out + o, r, a.vec != 0, nv);
+        tfbn_st4(a.out + o, r, a.vec != 0, nv);
     });
 }
 
@@ -290,28 +266,28 @@ __global__ __launch_bounds__(UL_BLOCK) void ul_dy_kernel(UlWalk a)
     ul_walk(a.rows, a.ncg, a.rb, a.dv, [&](long long row, int cg) {
         const int c = 4 * cg, nv = a.cout - c;
         const size_t o = (size_t)row * a.cout + c;
-        pair_f32x4 dz = ul_ld4(a.go + o, a.vec != 0, nv), dy = {0.f, 0.f, 0.f, 0.f};
+        pair_f32x4 dz = tfbn_ld4(a.go + o, a.vec != 0, nv), dy = {0.f, 0.f, 0.f, 0.f};
         if (a.act) {
-            const pair_f32x4 h = ul_ld4(a.out_in + o, a.vec != 0, nv);
+            const pair_f32x4 h = tfbn_ld4(a.out_in + o, a.vec != 0, nv);
 #pragma unroll
             for (int q = 0; q < 4; q++) dz[q] = dz[q] * pair_dact(a.act, h[q]);
         }
-        if (a.gs) ul_st4(a.gs + o, dz, a.vec != 0, nv);
+        if (a.gs) tfbn_st4(a.gs + o, dz, a.vec != 0, nv);
         if (!a.dy) return;
         if (a.bn_mode == 0) dy = dz;
         else {
-            const pair_f32x4 y = a.bn_mode == 1 ? ul_ld4(a.y + o, a.vec != 0, nv) : dz;
+            const pair_f32x4 y = a.bn_mode == 1 ? tfbn_ld4(a.y + o, a.vec != 0, nv) : dz;
 #pragma unroll
             for (int q = 0; q < 4; q++) {
                 if (q >= nv) continue;
                 const float invstd = a.invstd[c + q], gi = a.gamma[c + q] * invstd;
                 if (a.bn_mode == 1) {
-                    const float xh = ul_xhat(y[q], a.mean[c + q], invstd);
+                    const float xh = tfbn_xhat(y[q], a.mean[c + q], invstd);
                     dy[q] = gi * ((dz[q] - a.sums[c + q] * a.inv_n) - xh * (a.sums[a.cout + c + q] * a.inv_n));
                 } else dy[q] = gi * dz[q];
             }
         }
-        ul_st4(a.dy + o, dy, a.vec != 0, nv);
+        tfbn_st4(a.dy + o, dy, a.vec != 0, nv);
     });
 }
 
@@ -336,7 +312,7 @@ __global__ __launch_bounds__(UL_BLOCK) void ul_colsum_kernel(UlSums a)
             float dz = a.go[o];
             if (a.act) dz = dz * pair_dact(a.act, a.out[o]);
             s1 += (double)dz;
-            s2 += (double)(dz * ul_xhat(a.y[o], mean, invstd));
+            s2 += (double)(dz * tfbn_xhat(a.y[o], mean, invstd));
         }
     }
     red[0][g][cl] = s1; red[1][g][cl] = s2;
@@ -346,18 +322,6 @@ __global__ __launch_bounds__(UL_BLOCK) void ul_colsum_kernel(UlSums a)
         dst[0] = ((red[0][0][cl] + red[0][1][cl]) + red[0][2][cl]) + red[0][3][cl];
         dst[1] = ((red[1][0][cl] + red[1][1][cl]) + red[1][2][cl]) + red[1][3][cl];
     }
-}
-__global__ __launch_bounds__(UL_BLOCK) void ul_colsum_finalize_kernel(int cout, int nblocks, const double* __restrict__ part, float* __restrict__ sums,
-                                                                       float* __restrict__ grad_beta, float* __restrict__ grad_gamma)
-{
-    const int c = blockIdx.x * UL_BLOCK + threadIdx.x;
-    if (c >= cout) return;
-    double s1 = 0.0, s2 = 0.0;
-#pragma unroll 4
-    for (int b = 0; b < nblocks; b++) { s1 += part[((size_t)b * cout + c) * 2]; s2 += part[((size_t)b * cout + c) * 2 + 1]; }
-    sums[c] = (float)s1; sums[cout + c] = (float)s2;
-    if (grad_beta) grad_beta[c] = (float)s1;
-    if (grad_gamma) grad_gamma[c] = (float)s2;
 }
 
 struct UlDgrad {
@@ -526,11 +490,6 @@ inline UlPlan ul_plan(long long rows, int cin, int cout)
     return p;
 }
 inline bool ul_dims_ok(int cin, int cout) { return cin <= UL_MAX_C && cout <= UL_MAX_C; }
-inline char* ul_base(void* ws) { return reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255); }
-inline bool ul_vec(int c, const void* p0, const void* p1 = nullptr, const void* p2 = nullptr, const void* p3 = nullptr, const void* p4 = nullptr)
-{
-    return c % 4 == 0 && cbl_host_aligned16(p0) && cbl_host_aligned16(p1) && cbl_host_aligned16(p2) && cbl_host_aligned16(p3) && cbl_host_aligned16(p4);
-}
 inline void ul_walk_shape(UlWalk& a, unsigned* grid)
 {
     a.ncg = (a.cout + 3) / 4;
@@ -541,6 +500,34 @@ inline void ul_walk_shape(UlWalk& a, unsigned* grid)
 }
 
 // the launches the unary entries and the up_conv entries share
+// bn_mode 1 behind the forward product (which left y and the tiles' statistics in part): the batch statistics, then out = act(bn(y) (+ shortcut))
+inline void ul_launch_bn_tail(hipStream_t st, long long rows, int c_out, long long row_tiles, const float* part, float eps, float momentum, float* moving_mean,
+                              float* moving_var, float* save_mean, float* save_invstd, const float* gamma, const float* beta, int activation, const float* y,
+                              const float* shortcut, float* out)
+{
+    hipLaunchKernelGGL(ul_stats_finalize_kernel, dim3(cbl_div_up(c_out, 32)), dim3(UL_BLOCK), 0, st, rows, c_out, row_tiles, part, eps, momentum, moving_mean, moving_var,
+                       save_mean, save_invstd);
+    UlWalk a = {};
+    a.rows = rows; a.cout = c_out; a.act = activation; a.bn_mode = 1;
+    a.vec = tfbn_vec(c_out, y, out, shortcut);
+    a.y = y; a.mean = save_mean; a.invstd = save_invstd; a.gamma = gamma; a.beta = beta; a.shortcut = shortcut; a.out = out;
+    unsigned g;
+    ul_walk_shape(a, &g);
+    hipLaunchKernelGGL(ul_normalize_kernel, dim3(g), dim3(UL_BLOCK), 0, st, a);
+}
+// backward: dz = grad_out * act'(out) -> grad_shortcut (optional), dz through the batch norm -> dy (optional); sums: ul_launch_colsums' (bn_mode 1)
+inline void ul_launch_dy(hipStream_t st, long long rows, int c_out, int bn_mode, int activation, const float* grad_out, const float* out, const float* y,
+                         const float* save_mean, const float* save_invstd, const float* gamma, const float* sums, float* dy, float* grad_shortcut)
+{
+    UlWalk a = {};
+    a.rows = rows; a.cout = c_out; a.act = activation; a.bn_mode = bn_mode; a.inv_n = (float)(1.0 / (double)rows);
+    a.dy = dy;
+    a.vec = tfbn_vec(c_out, grad_out, out, y, dy, grad_shortcut);
+    a.go = grad_out; a.out_in = out; a.y = y; a.mean = save_mean; a.invstd = save_invstd; a.gamma = gamma; a.sums = sums; a.gs = grad_shortcut;
+    unsigned g;
+    ul_walk_shape(a, &g);
+    hipLaunchKernelGGL(ul_dy_kernel, dim3(g), dim3(UL_BLOCK), 0, st, a);
+}
 inline void ul_launch_colsums(hipStream_t st, long long rows, int c_out, int activation, const float* grad_out, const float* out, const float* y,
                               const float* save_mean, const float* save_invstd, int sum_blocks, double* part, float* sums, float* grad_beta, float* grad_gamma)
 {
@@ -549,12 +536,12 @@ inline void ul_launch_colsums(hipStream_t st, long long rows, int c_out, int act
     s.go = grad_out; s.out = out; s.y = y; s.mean = save_mean; s.invstd = save_invstd;
     s.part = part;
     hipLaunchKernelGGL(ul_colsum_kernel, dim3(sum_blocks, cbl_div_up(c_out, 64)), dim3(UL_BLOCK), 0, st, s);
-    hipLaunchKernelGGL(ul_colsum_finalize_kernel, dim3(cbl_div_up(c_out, UL_BLOCK)), dim3(UL_BLOCK), 0, st, c_out, sum_blocks, s.part, sums, grad_beta, grad_gamma);
+    tfbn_launch_sums_finalize(st, c_out, sum_blocks, s.part, sums, grad_beta, grad_gamma);
 }
 inline void ul_launch_dgrad(hipStream_t st, long long rows, int c_in, int c_out, const float* dy, const float* weights, float* grad_x)
 {
     UlDgrad d;
-    d.rows = rows; d.row_tiles = (rows + UL_T - 1) / UL_T; d.cin = c_in; d.cout = c_out; d.veca = ul_vec(c_out, dy); d.vecb = ul_vec(c_out, weights);
+    d.rows = rows; d.row_tiles = (rows + UL_T - 1) / UL_T; d.cin = c_in; d.cout = c_out; d.veca = tfbn_vec(c_out, dy); d.vecb = tfbn_vec(c_out, weights);
     d.dy = dy; d.w = weights; d.gx = grad_x;
     const dim3 grid((unsigned)(d.row_tiles > UL_ROW_BLOCKS ? UL_ROW_BLOCKS : d.row_tiles), cbl_div_up(c_in, UL_T));
     hipLaunchKernelGGL(ul_dgrad_kernel, grid, dim3(UL_BLOCK), 0, st, d);
@@ -564,7 +551,7 @@ inline void ul_launch_wgrad(hipStream_t st, const UlPlan& p, long long rows, int
                             float* grad_biases, float* wpart)
 {
     UlWgrad w;
-    w.rows = rows; w.chunk_rows = p.chunk_rows; w.cin = c_in; w.cout = c_out; w.veca = ul_vec(c_in, x); w.vecb = ul_vec(c_out, dy);
+    w.rows = rows; w.chunk_rows = p.chunk_rows; w.cin = c_in; w.cout = c_out; w.veca = tfbn_vec(c_in, x); w.vecb = tfbn_vec(c_out, dy);
     w.tiles_n = (int)cbl_div_up(c_out, UL_T);
     w.x = x; w.dy = dy; w.gw = grad_weights; w.gb = grad_biases;
     w.partial = p.nchunks > 1 ? wpart : nullptr;

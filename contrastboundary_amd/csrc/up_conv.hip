@@ -34,7 +34,7 @@ template <bool B_KC>
 inline void ul_launch_split(hipStream_t st, long long M, int N, int K, int splits, int kspan, const float* A, const float* B, float* part, float* out)
 {
     UlSplit s;
-    s.M = M; s.row_tiles = (M + UL_T - 1) / UL_T; s.N = N; s.K = K; s.kspan = kspan; s.veca = ul_vec(K, A); s.vecb = ul_vec(B_KC ? K : N, B);
+    s.M = M; s.row_tiles = (M + UL_T - 1) / UL_T; s.N = N; s.K = K; s.kspan = kspan; s.veca = tfbn_vec(K, A); s.vecb = tfbn_vec(B_KC ? K : N, B);
     s.A = A; s.B = B; s.part = part;
     hipLaunchKernelGGL(ul_split_product_kernel<B_KC>, dim3((unsigned)s.row_tiles, cbl_div_up(N, UL_T), splits), dim3(UL_BLOCK), 0, st, s);
     hipLaunchKernelGGL(ul_split_combine_kernel, dim3(cbl_grid_for(M * N, UL_BLOCK)), dim3(UL_BLOCK), 0, st, (size_t)M * N, splits, part, out);
@@ -82,21 +82,18 @@ CBL_EXPORT int cbl_up_conv_forward(long long n2, long long n1, int c_up, int c_s
                                    float* moving_mean, float* moving_var, int activation, float* save_mean, float* save_invstd, float* y, float* out,
                                    void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (bn_mode < 0 || bn_mode > 2 || activation < 0 || activation > 2) return CBL_ERR_BAD_ARG;
+    if (!tfbn_modes_ok(bn_mode, activation)) return CBL_ERR_BAD_ARG;
     if (const int rc = up_check(n2, n1, c_up, c_skip, c_out, k)) return rc;
     if (n2 == 0) return CBL_OK;
-    if (!coarse || !up_inds || !skip || !weights || !out) return CBL_ERR_BAD_ARG;
-    if (bn_mode != 0 && (!gamma || !beta || !save_mean || !save_invstd || !y || !(eps > 0.f))) return CBL_ERR_BAD_ARG;
-    if (bn_mode == 2 && (!moving_mean || !moving_var)) return CBL_ERR_BAD_ARG;
-    if (bn_mode == 1 && ((moving_mean == nullptr) != (moving_var == nullptr))) return CBL_ERR_BAD_ARG;
+    if (!coarse || !up_inds || !skip || !weights || !out || (bn_mode != 0 && !y)) return CBL_ERR_BAD_ARG;
+    if (const int rc = tfbn_check_forward(bn_mode, gamma, beta, eps, moving_mean, moving_var, save_mean, save_invstd)) return rc;
     const UpPlan p = up_plan(n2, n1, c_up, c_skip, c_out);
     if (!workspace || workspace_bytes < p.bytes) return CBL_ERR_WORKSPACE;
     hipStream_t st = cbl_stream(stream);
-    char* base = ul_base(workspace);
+    char* base = tfbn_base(workspace);
     float* P = reinterpret_cast<float*>(base + p.off_p);
     const float* w_skip = weights + (size_t)c_up * c_out;           // (c_up * c_out may be no multiple of 4: then the scalar-load path)
-    if (bn_mode == 2)
-        hipLaunchKernelGGL(ul_moving_stats_kernel, dim3(cbl_div_up(c_out, UL_BLOCK)), dim3(UL_BLOCK), 0, st, c_out, moving_mean, moving_var, eps, save_mean, save_invstd);
+    if (bn_mode == 2) tfbn_launch_moving_stats(st, c_out, moving_mean, moving_var, eps, save_mean, save_invstd);
     const unsigned col_tiles = cbl_div_up(c_out, UL_T);
     UlForward f = {};
     f.cout = c_out;
@@ -104,29 +101,20 @@ CBL_EXPORT int cbl_up_conv_forward(long long n2, long long n1, int c_up, int c_s
         ul_launch_split<false>(st, n1, c_out, c_up, p.split_p, p.kspan_p, coarse, weights, reinterpret_cast<float*>(base + p.off_split), P);
     else {
         f.rows = n1; f.row_tiles = p.up.row_tiles; f.cin = c_up;
-        f.veca = ul_vec(c_up, coarse); f.vecb = ul_vec(c_out, weights);
+        f.veca = tfbn_vec(c_up, coarse); f.vecb = tfbn_vec(c_out, weights);
         f.fuse = 1; f.bn = 0; f.act = 0;
         f.x = coarse; f.w = weights; f.out = P;
         hipLaunchKernelGGL(ul_forward_kernel<false>, dim3((unsigned)(f.row_tiles > UL_ROW_BLOCKS ? UL_ROW_BLOCKS : f.row_tiles), col_tiles), dim3(UL_BLOCK), 0, st, f);
     }
     f.rows = n2; f.row_tiles = p.skip.row_tiles; f.cin = c_skip;
-    f.veca = ul_vec(c_skip, skip); f.vecb = ul_vec(c_out, w_skip);
+    f.veca = tfbn_vec(c_skip, skip); f.vecb = tfbn_vec(c_out, w_skip);
     f.fuse = bn_mode != 1; f.bn = bn_mode != 0; f.act = activation;
     f.x = skip; f.w = w_skip; f.bias = biases; f.mean = save_mean; f.invstd = save_invstd; f.gamma = gamma; f.beta = beta;
     f.y = y; f.out = out; f.part = bn_mode == 1 ? reinterpret_cast<float*>(base + p.skip.off_part) : nullptr;
     f.up_p = P; f.up_idx = up_inds; f.up_n1 = n1; f.up_k = k;
     hipLaunchKernelGGL(ul_forward_kernel<true>, dim3((unsigned)(f.row_tiles > UL_ROW_BLOCKS ? UL_ROW_BLOCKS : f.row_tiles), col_tiles), dim3(UL_BLOCK), 0, st, f);
-    if (bn_mode == 1) {
-        hipLaunchKernelGGL(ul_stats_finalize_kernel, dim3(cbl_div_up(c_out, 32)), dim3(UL_BLOCK), 0, st, n2, c_out, p.skip.row_tiles, f.part, eps, momentum, moving_mean,
-                           moving_var, save_mean, save_invstd);
-        UlWalk a = {};
-        a.rows = n2; a.cout = c_out; a.act = activation; a.bn_mode = 1;
-        a.vec = ul_vec(c_out, y, out);
-        a.y = y; a.mean = save_mean; a.invstd = save_invstd; a.gamma = gamma; a.beta = beta; a.out = out;
-        unsigned g;
-        ul_walk_shape(a, &g);
-        hipLaunchKernelGGL(ul_normalize_kernel, dim3(g), dim3(UL_BLOCK), 0, st, a);
-    }
+    if (bn_mode == 1)
+        ul_launch_bn_tail(st, n2, c_out, p.skip.row_tiles, f.part, eps, momentum, moving_mean, moving_var, save_mean, save_invstd, gamma, beta, activation, y, nullptr, out);
     return cbl_status();
 }
 
@@ -137,19 +125,17 @@ CBL_EXPORT int cbl_up_conv_backward(long long n2, long long n1, int c_up, int c_
                                     void* workspace, size_t workspace_bytes, void* stream)
 {
     (void)up_inds;                                                  // the backward pass walks the transposed table, never the table itself
-    if (bn_mode < 0 || bn_mode > 2 || activation < 0 || activation > 2) return CBL_ERR_BAD_ARG;
+    if (!tfbn_modes_ok(bn_mode, activation)) return CBL_ERR_BAD_ARG;
     if (const int rc = up_check(n2, n1, c_up, c_skip, c_out, k)) return rc;
     if (n2 == 0) return CBL_OK;
-    if (!coarse || !skip || !weights || !grad_out) return CBL_ERR_BAD_ARG;
-    if (activation != 0 && !out) return CBL_ERR_BAD_ARG;
-    if (bn_mode != 0 && (!gamma || !save_mean || !save_invstd || !y)) return CBL_ERR_BAD_ARG;
-    if (bn_mode == 0 && (grad_gamma || grad_beta)) return CBL_ERR_BAD_ARG;
+    if (!coarse || !skip || !weights || !grad_out || (bn_mode != 0 && !y)) return CBL_ERR_BAD_ARG;
+    if (const int rc = tfbn_check_backward(bn_mode, activation, gamma, save_mean, save_invstd, out, grad_gamma, grad_beta)) return rc;
     const bool coarse_side = grad_coarse || grad_weights;
     if (coarse_side && (!inv_start || !inv_src)) return CBL_ERR_BAD_ARG;
     const UpPlan p = up_plan(n2, n1, c_up, c_skip, c_out);
     if (!workspace || workspace_bytes < p.bytes) return CBL_ERR_WORKSPACE;
     hipStream_t st = cbl_stream(stream);
-    char* base = ul_base(workspace);
+    char* base = tfbn_base(workspace);
     float* sums = reinterpret_cast<float*>(base + p.skip.off_sums);
     const bool products = coarse_side || grad_skip || grad_biases;
     if (bn_mode == 1 ? (products || grad_gamma || grad_beta) : (grad_gamma || grad_beta))
@@ -158,16 +144,8 @@ CBL_EXPORT int cbl_up_conv_backward(long long n2, long long n1, int c_up, int c_
     if (!products) return cbl_status();
     const bool identity = bn_mode == 0 && activation == 0;
     const float* dy = identity ? grad_out : reinterpret_cast<float*>(base + p.skip.off_dy);
-    if (!identity) {
-        UlWalk a = {};
-        a.rows = n2; a.cout = c_out; a.act = activation; a.bn_mode = bn_mode; a.inv_n = (float)(1.0 / (double)n2);
-        a.dy = const_cast<float*>(dy);
-        a.vec = ul_vec(c_out, grad_out, out, y, a.dy);
-        a.go = grad_out; a.out_in = out; a.y = y; a.mean = save_mean; a.invstd = save_invstd; a.gamma = gamma; a.sums = sums;
-        unsigned g;
-        ul_walk_shape(a, &g);
-        hipLaunchKernelGGL(ul_dy_kernel, dim3(g), dim3(UL_BLOCK), 0, st, a);
-    }
+    if (!identity)
+        ul_launch_dy(st, n2, c_out, bn_mode, activation, grad_out, out, y, save_mean, save_invstd, gamma, sums, const_cast<float*>(dy), nullptr);
     const float* w_skip = weights + (size_t)c_up * c_out;
     if (coarse_side) {
         float* dyc = reinterpret_cast<float*>(base + p.off_p);

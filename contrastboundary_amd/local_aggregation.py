@@ -382,7 +382,7 @@ def adaptive_weight(query_points, support_points, neighbors_indices, features, r
                                         softmax, red)
 
 
-def _fan_in_init_(weights):
+def fan_in_init_(weights):
     """tf.contrib.layers.variance_scaling_initializer(factor=1.0, mode='FAN_IN', uniform=False): a normal of standard deviation sqrt(1.3 / fan_in)
     truncated at two standard deviations; fan_in = the rows of a TF (in, out) weight"""
     std = (1.3 / weights.shape[0]) ** 0.5
@@ -405,11 +405,11 @@ class AdaptiveWeight(torch.nn.Module):
         self.local_input_feature, self.shared_channels, self.fc_num = local_input_feature, shared_channels, fc_num
         self.weight_softmax, self.reduction, self.activation_fn = weight_softmax, reduction, activation_fn
         self.weights = torch.nn.Parameter(torch.empty(d_in, M))
-        _fan_in_init_(self.weights)
+        fan_in_init_(self.weights)
         self.biases = torch.nn.Parameter(torch.zeros(M))
         for l in range(1, fc_num):
             w = torch.nn.Parameter(torch.empty(M, M))
-            _fan_in_init_(w)
+            fan_in_init_(w)
             setattr(self, "weights_{}".format(l), w)
             setattr(self, "biases_{}".format(l), torch.nn.Parameter(torch.zeros(M)))
 
@@ -831,7 +831,7 @@ class _IndMaxPool(Function):
 _first_columns = collections.OrderedDict()     # neighbour table -> (the table, its contiguous first column), the 16 most recent
 
 
-def _first_column(inds):
+def first_column(inds):
     """inds[:, :1] as a tensor of its own, the SAME one for the same table from call to call: the transposed table built for it (neighbor_state's registry,
     keyed by the tensor) is then found again by every later backward pass instead of being built per call"""
     if inds.shape[1] == 1:
@@ -857,7 +857,7 @@ class _IndClosestPool(Function):
     @staticmethod
     def forward(ctx, x, inds):
         out = _ind_closest_pool_forward(x, inds)
-        ctx.save_for_backward(_first_column(inds))
+        ctx.save_for_backward(first_column(inds))
         ctx.shape = tuple(x.shape)
         return out
 

@@ -12,7 +12,7 @@ import torch
 from torch.autograd import Function
 
 from . import _lib
-from .local_aggregation import _fan_in_init_, _first_column
+from .local_aggregation import fan_in_init_, first_column
 
 _i = ctypes.c_int
 _f = ctypes.c_float
@@ -27,25 +27,76 @@ def _chk(t, name):
     return t
 
 
-def _workspace(L, rows, c_in, c_out, dev):
-    return torch.empty(max(L.cbl_unary_layer_workspace_bytes(_ll(rows), _i(c_in), _i(c_out)), 1), dtype=torch.uint8, device=dev)
+def _chk_optional(**named):
+    """_chk of the arguments that are given, in their order.  Types come before every check of a shape, which is why this is not part of _bn_mode"""
+    for name, t in named.items():
+        if t is not None:
+            _chk(t, name)
+
+
+def _bn_mode(op, c_out, gamma, beta, moving_mean, moving_variance, is_training, biases=None):
+    """The TF batch norm's arguments of an op (and its biases): which come together, then their lengths.  -> bn_mode (0: none, 1: batch statistics, 2: the
+    moving ones), the convention of csrc/tf_bn.h"""
+    if (gamma is None) != (beta is None):
+        raise ValueError("{}: gamma and beta come together (both None: bn=False)".format(op))
+    if gamma is None and (moving_mean is not None or moving_variance is not None):
+        raise ValueError("{}: moving statistics without a batch norm".format(op))
+    if (moving_mean is None) != (moving_variance is None):
+        raise ValueError("{}: moving_mean and moving_variance come together".format(op))
+    if gamma is not None and not is_training and moving_mean is None:
+        raise ValueError("{}: is_training=False needs moving_mean and moving_variance".format(op))
+    for t, name in ((biases, "biases"), (gamma, "gamma"), (beta, "beta"), (moving_mean, "moving_mean"), (moving_variance, "moving_variance")):
+        if t is not None and tuple(t.shape) != (c_out,):
+            raise ValueError("{}: {} of shape {}, ({},) expected".format(op, name, tuple(t.shape), c_out))
+    return 0 if gamma is None else (1 if is_training else 2)
+
+
+def _bn_variables(module, fdim, bn):
+    """the reference's four batch-norm variables on a module (TF names): `gamma` (ones), `beta` (zeros), the buffers `moving_mean` (zeros) / `moving_variance`
+    (ones); bn=False: all four None"""
+    if bn:
+        module.gamma = torch.nn.Parameter(torch.ones(fdim))
+        module.beta = torch.nn.Parameter(torch.zeros(fdim))
+        module.register_buffer("moving_mean", torch.zeros(fdim))
+        module.register_buffer("moving_variance", torch.ones(fdim))
+    else:
+        module.gamma = module.beta = module.moving_mean = module.moving_variance = None
+
+
+# What the three Functions below share.  `moving` is the tuple (moving_mean, moving_variance), which the kernels update in place under bn_mode 1: buffers, not
+# inputs of the differentiated function, so they travel as one plain Python object and autograd never sees an input modified in place
+def _allocator(dev):
+    return lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+
+
+def _workspace(entry, dev, *args):
+    """entry: an op's cbl_*_workspace_bytes, args: its arguments"""
+    return torch.empty(max(entry(*args), 1), dtype=torch.uint8, device=dev)
+
+
+def _wanted(new, *specs):
+    """(wanted, shape), ... -> a new tensor of that shape, or None where the gradient is not wanted"""
+    return tuple(new(*shape) if wanted else None for wanted, shape in specs)
+
+
+def _zeroed(*grads):
+    """no rows: a gradient that is a sum over the rows is zero (nothing is launched)"""
+    for g in grads:
+        if g is not None:
+            g.zero_()
 
 
 class _Conv1d1x1(Function):
     @staticmethod
     def forward(ctx, features, weights, biases, gamma, beta, shortcut, moving, bn_mode, act, momentum, eps):
-        # moving: the tuple (moving_mean, moving_variance), which the kernels update in place under bn_mode 1.  They are buffers, not inputs of the
-        # differentiated function, so they travel as one plain Python object and autograd never sees an input modified in place
         moving_mean, moving_variance = moving
         L = _lib.lib()
         rows, c_in = features.shape
         c_out = weights.shape[1]
-        dev = features.device
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        new = _allocator(features.device)
         out = new(rows, c_out)
-        y = new(rows, c_out) if bn_mode else None
-        save_mean, save_invstd = (new(c_out), new(c_out)) if bn_mode else (None, None)
-        ws = _workspace(L, rows, c_in, c_out, dev) if bn_mode == 1 else None
+        y, save_mean, save_invstd = _wanted(new, (bn_mode, (rows, c_out)), (bn_mode, (c_out,)), (bn_mode, (c_out,)))
+        ws = _workspace(L.cbl_unary_layer_workspace_bytes, features.device, _ll(rows), _i(c_in), _i(c_out)) if bn_mode == 1 else None
         _lib.check(L.cbl_unary_layer_forward(_ll(rows), _i(c_in), _i(c_out), _lib.ptr(features), _lib.ptr(weights), _lib.ptr(biases), _lib.ptr(shortcut),
                                              _i(bn_mode), _lib.ptr(gamma), _lib.ptr(beta), _f(eps), _f(momentum), _lib.ptr(moving_mean),
                                              _lib.ptr(moving_variance), _i(act), _lib.ptr(save_mean), _lib.ptr(save_invstd), _lib.ptr(y), _lib.ptr(out),
@@ -62,22 +113,14 @@ class _Conv1d1x1(Function):
         L = _lib.lib()
         rows, c_in = features.shape
         c_out = weights.shape[1]
-        dev = features.device
         grad_out = grad_out.contiguous()
         need = ctx.needs_input_grad
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        gx = new(rows, c_in) if need[0] else None
-        gw = new(c_in, c_out) if need[1] else None
-        gb = new(c_out) if has_bias and need[2] else None
-        gg = new(c_out) if bn_mode and need[3] else None
-        gbeta = new(c_out) if bn_mode and need[4] else None
-        gs = new(rows, c_out) if has_shortcut and need[5] else None
+        gx, gw, gb, gg, gbeta, gs = _wanted(_allocator(features.device), (need[0], (rows, c_in)), (need[1], (c_in, c_out)), (has_bias and need[2], (c_out,)),
+                                            (bn_mode and need[3], (c_out,)), (bn_mode and need[4], (c_out,)), (has_shortcut and need[5], (rows, c_out)))
         if rows == 0:
-            for g in (gw, gb, gg, gbeta):
-                if g is not None:
-                    g.zero_()
+            _zeroed(gw, gb, gg, gbeta)
             return (gx, gw, gb, gg, gbeta, gs) + (None,) * 5
-        ws = _workspace(L, rows, c_in, c_out, dev)
+        ws = _workspace(L.cbl_unary_layer_workspace_bytes, features.device, _ll(rows), _i(c_in), _i(c_out))
         _lib.check(L.cbl_unary_layer_backward(_ll(rows), _i(c_in), _i(c_out), _lib.ptr(features), _lib.ptr(weights), _i(bn_mode), _lib.ptr(gamma),
                                               _lib.ptr(save_mean), _lib.ptr(save_invstd), _i(act), _lib.ptr(y), _lib.ptr(out), _lib.ptr(grad_out),
                                               _lib.ptr(gx), _lib.ptr(gw), _lib.ptr(gb), _lib.ptr(gg), _lib.ptr(gbeta), _lib.ptr(gs), _lib.ptr(ws),
@@ -92,29 +135,15 @@ def conv1d_1x1(features, weights, biases=None, gamma=None, beta=None, moving_mea
     not; shortcut (rows, c_out): added before the activation, which makes one call the tail of a bottleneck.  Runs on the current stream of the tensors'
     device; 1 <= c_in, c_out <= 4096."""
     _chk(features, "features"); _chk(weights, "weights")
-    for t, name in ((biases, "biases"), (gamma, "gamma"), (beta, "beta"), (moving_mean, "moving_mean"), (moving_variance, "moving_variance"),
-                    (shortcut, "shortcut")):
-        if t is not None:
-            _chk(t, name)
+    _chk_optional(biases=biases, gamma=gamma, beta=beta, moving_mean=moving_mean, moving_variance=moving_variance, shortcut=shortcut)
     if features.dim() != 2 or weights.dim() != 2 or features.shape[1] != weights.shape[0]:
         raise ValueError("conv1d_1x1: features {} and weights {}: (rows, c_in) and (c_in, c_out) expected".format(tuple(features.shape), tuple(weights.shape)))
     c_in, c_out = weights.shape
     if not (1 <= c_in <= MAX_WIDTH and 1 <= c_out <= MAX_WIDTH):
         raise NotImplementedError("conv1d_1x1: widths {} -> {} (1 to {} each)".format(c_in, c_out, MAX_WIDTH))
-    if (gamma is None) != (beta is None):
-        raise ValueError("conv1d_1x1: gamma and beta come together (both None: bn=False)")
-    if gamma is None and (moving_mean is not None or moving_variance is not None):
-        raise ValueError("conv1d_1x1: moving statistics without a batch norm")
-    if (moving_mean is None) != (moving_variance is None):
-        raise ValueError("conv1d_1x1: moving_mean and moving_variance come together")
-    if gamma is not None and not is_training and moving_mean is None:
-        raise ValueError("conv1d_1x1: is_training=False needs moving_mean and moving_variance")
-    for t, name in ((biases, "biases"), (gamma, "gamma"), (beta, "beta"), (moving_mean, "moving_mean"), (moving_variance, "moving_variance")):
-        if t is not None and tuple(t.shape) != (c_out,):
-            raise ValueError("conv1d_1x1: {} of shape {}, ({},) expected".format(name, tuple(t.shape), c_out))
+    bn_mode = _bn_mode("conv1d_1x1", c_out, gamma, beta, moving_mean, moving_variance, is_training, biases)
     if shortcut is not None and tuple(shortcut.shape) != (features.shape[0], c_out):
         raise ValueError("conv1d_1x1: shortcut of shape {}, ({}, {}) expected".format(tuple(shortcut.shape), features.shape[0], c_out))
-    bn_mode = 0 if gamma is None else (1 if is_training else 2)
     return _Conv1d1x1.apply(features, weights, biases, gamma, beta, shortcut, (moving_mean, moving_variance), bn_mode, _ACTIVATIONS.get(activation_fn, 0),
                             float(bn_momentum), float(bn_eps))
 
@@ -134,15 +163,9 @@ class Conv1d1x1(torch.nn.Module):
         if init == "xavier":
             torch.nn.init.xavier_uniform_(self.weights)
         else:
-            _fan_in_init_(self.weights)
+            fan_in_init_(self.weights)
         self.biases = torch.nn.Parameter(torch.zeros(out_fdim)) if with_bias else None
-        if bn:
-            self.gamma = torch.nn.Parameter(torch.ones(out_fdim))
-            self.beta = torch.nn.Parameter(torch.zeros(out_fdim))
-            self.register_buffer("moving_mean", torch.zeros(out_fdim))
-            self.register_buffer("moving_variance", torch.ones(out_fdim))
-        else:
-            self.gamma = self.beta = self.moving_mean = self.moving_variance = None
+        _bn_variables(self, out_fdim, bn)
 
     def tf_scopes(self):
         """variable name -> its TF variable scope (:223-235): weights / biases in the layer's own scope, the batch norm's variables under bn/"""
@@ -163,14 +186,11 @@ class Conv1d1x1(torch.nn.Module):
 class _PoolBN(Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, moving, bn_mode, act, momentum, eps):
-        # (moving: as in _Conv1d1x1)
         moving_mean, moving_variance = moving
         L = _lib.lib()
         rows, C = x.shape
-        dev = x.device
-        out = torch.empty_like(x)
-        save_mean, save_invstd = (torch.empty(C, dtype=torch.float32, device=dev) for _ in range(2)) if bn_mode else (None, None)
-        ws = _pool_bn_workspace(L, rows, C, dev) if bn_mode == 1 else None
+        out, save_mean, save_invstd = _wanted(_allocator(x.device), (True, (rows, C)), (bn_mode, (C,)), (bn_mode, (C,)))
+        ws = _workspace(L.cbl_pool_bn_workspace_bytes, x.device, _ll(rows), _i(C)) if bn_mode == 1 else None
         _lib.check(L.cbl_pool_bn_forward(_ll(rows), _i(C), _lib.ptr(x), _i(bn_mode), _lib.ptr(gamma), _lib.ptr(beta), _f(eps), _f(momentum),
                                          _lib.ptr(moving_mean), _lib.ptr(moving_variance), _i(act), _lib.ptr(save_mean), _lib.ptr(save_invstd), _lib.ptr(out),
                                          _lib.ptr(ws), ctypes.c_size_t(ws.numel() if ws is not None else 0), _lib.stream_of(x)), "cbl_pool_bn_forward")
@@ -184,26 +204,17 @@ class _PoolBN(Function):
         bn_mode, act = ctx.cfg
         L = _lib.lib()
         rows, C = x.shape
-        dev = x.device
         grad_out = grad_out.contiguous()
         need = ctx.needs_input_grad
-        gx = torch.empty_like(x) if need[0] else None
-        gg = torch.empty(C, dtype=torch.float32, device=dev) if bn_mode and need[1] else None
-        gbeta = torch.empty(C, dtype=torch.float32, device=dev) if bn_mode and need[2] else None
+        gx, gg, gbeta = _wanted(_allocator(x.device), (need[0], (rows, C)), (bn_mode and need[1], (C,)), (bn_mode and need[2], (C,)))
         if rows == 0:
-            for g in (gg, gbeta):
-                if g is not None:
-                    g.zero_()
+            _zeroed(gg, gbeta)
             return (gx, gg, gbeta) + (None,) * 5
-        ws = _pool_bn_workspace(L, rows, C, dev) if bn_mode else None
+        ws = _workspace(L.cbl_pool_bn_workspace_bytes, x.device, _ll(rows), _i(C)) if bn_mode else None
         _lib.check(L.cbl_pool_bn_backward(_ll(rows), _i(C), _lib.ptr(x), _i(bn_mode), _lib.ptr(gamma), _lib.ptr(save_mean), _lib.ptr(save_invstd), _i(act),
                                           _lib.ptr(out), _lib.ptr(grad_out), _lib.ptr(gx), _lib.ptr(gg), _lib.ptr(gbeta), _lib.ptr(ws),
                                           ctypes.c_size_t(ws.numel() if ws is not None else 0), _lib.stream_of(x)), "cbl_pool_bn_backward")
         return (gx, gg, gbeta) + (None,) * 5
-
-
-def _pool_bn_workspace(L, rows, C, dev):
-    return torch.empty(max(L.cbl_pool_bn_workspace_bytes(_ll(rows), _i(C)), 1), dtype=torch.uint8, device=dev)
 
 
 def pool_bn(x, gamma=None, beta=None, moving_mean=None, moving_variance=None, *, is_training=True, activation_fn="relu", bn_momentum=0.98, bn_eps=1e-3):
@@ -212,26 +223,13 @@ def pool_bn(x, gamma=None, beta=None, moving_mean=None, moving_variance=None, *,
     beta: the batch norm (gamma None: bn=False, the activation alone); moving_mean / moving_variance: updated in place when training (TF convention), used
     when not.  Runs on the current stream of the tensors' device; 1 <= C <= 4096.  There is no fallback: CPU tensors raise."""
     _chk(x, "x")
-    for t, name in ((gamma, "gamma"), (beta, "beta"), (moving_mean, "moving_mean"), (moving_variance, "moving_variance")):
-        if t is not None:
-            _chk(t, name)
+    _chk_optional(gamma=gamma, beta=beta, moving_mean=moving_mean, moving_variance=moving_variance)
     if x.dim() != 2:
         raise ValueError("pool_bn: x of shape {}, (rows, C) expected".format(tuple(x.shape)))
     C = x.shape[1]
     if not 1 <= C <= MAX_WIDTH:
         raise NotImplementedError("pool_bn: width {} (1 to {})".format(C, MAX_WIDTH))
-    if (gamma is None) != (beta is None):
-        raise ValueError("pool_bn: gamma and beta come together (both None: bn=False)")
-    if gamma is None and (moving_mean is not None or moving_variance is not None):
-        raise ValueError("pool_bn: moving statistics without a batch norm")
-    if (moving_mean is None) != (moving_variance is None):
-        raise ValueError("pool_bn: moving_mean and moving_variance come together")
-    if gamma is not None and not is_training and moving_mean is None:
-        raise ValueError("pool_bn: is_training=False needs moving_mean and moving_variance")
-    for t, name in ((gamma, "gamma"), (beta, "beta"), (moving_mean, "moving_mean"), (moving_variance, "moving_variance")):
-        if t is not None and tuple(t.shape) != (C,):
-            raise ValueError("pool_bn: {} of shape {}, ({},) expected".format(name, tuple(t.shape), C))
-    bn_mode = 0 if gamma is None else (1 if is_training else 2)
+    bn_mode = _bn_mode("pool_bn", C, gamma, beta, moving_mean, moving_variance, is_training)
     return _PoolBN.apply(x, gamma, beta, (moving_mean, moving_variance), bn_mode, _ACTIVATIONS.get(activation_fn, 0), float(bn_momentum), float(bn_eps))
 
 
@@ -244,13 +242,7 @@ class PoolBN(torch.nn.Module):
         if not 1 <= fdim <= MAX_WIDTH:
             raise NotImplementedError("PoolBN: width {} (1 to {})".format(fdim, MAX_WIDTH))
         self.activation_fn, self.bn_momentum, self.bn_eps, self.scope = activation_fn, bn_momentum, bn_eps, scope
-        if bn:
-            self.gamma = torch.nn.Parameter(torch.ones(fdim))
-            self.beta = torch.nn.Parameter(torch.zeros(fdim))
-            self.register_buffer("moving_mean", torch.zeros(fdim))
-            self.register_buffer("moving_variance", torch.ones(fdim))
-        else:
-            self.gamma = self.beta = self.moving_mean = self.moving_variance = None
+        _bn_variables(self, fdim, bn)
 
     def tf_scopes(self):
         """variable name -> its TF variable scope: all four under the layer's name (tf.layers.batch_normalization(name=scope))"""
@@ -262,29 +254,22 @@ class PoolBN(torch.nn.Module):
 
 
 # ---------------------------------------------------------------------------------------------- the segmentation head's decoder step
-def _up_workspace(L, n2, n1, c_up, c_skip, c_out, dev):
-    return torch.empty(max(L.cbl_up_conv_workspace_bytes(_ll(n2), _ll(n1), _i(c_up), _i(c_skip), _i(c_out)), 1), dtype=torch.uint8, device=dev)
-
-
 class _UpConv(Function):
     @staticmethod
     def forward(ctx, coarse, inds, skip, weights, biases, gamma, beta, moving, bn_mode, act, momentum, eps):
-        # (moving: as in _Conv1d1x1)
         moving_mean, moving_variance = moving
         L = _lib.lib()
         (n1, c_up), (n2, c_skip), c_out, k = coarse.shape, skip.shape, weights.shape[1], inds.shape[1]
-        dev = coarse.device
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        new = _allocator(coarse.device)
         out = new(n2, c_out)
-        y = new(n2, c_out) if bn_mode else None
-        save_mean, save_invstd = (new(c_out), new(c_out)) if bn_mode else (None, None)
-        ws = _up_workspace(L, n2, n1, c_up, c_skip, c_out, dev)
+        y, save_mean, save_invstd = _wanted(new, (bn_mode, (n2, c_out)), (bn_mode, (c_out,)), (bn_mode, (c_out,)))
+        ws = _workspace(L.cbl_up_conv_workspace_bytes, coarse.device, _ll(n2), _ll(n1), _i(c_up), _i(c_skip), _i(c_out))
         _lib.check(L.cbl_up_conv_forward(_ll(n2), _ll(n1), _i(c_up), _i(c_skip), _i(c_out), _lib.ptr(coarse), _lib.ptr(inds), _i(k), _lib.ptr(skip),
                                          _lib.ptr(weights), _lib.ptr(biases), _i(bn_mode), _lib.ptr(gamma), _lib.ptr(beta), _f(eps), _f(momentum),
                                          _lib.ptr(moving_mean), _lib.ptr(moving_variance), _i(act), _lib.ptr(save_mean), _lib.ptr(save_invstd), _lib.ptr(y),
                                          _lib.ptr(out), _lib.ptr(ws), ctypes.c_size_t(ws.numel()), _lib.stream_of(coarse)), "cbl_up_conv_forward")
         # the table's first column as the tensor the transposed table is registered under: built once per table, found again by every later backward pass
-        ctx.save_for_backward(coarse, _first_column(inds), skip, weights, gamma, save_mean, save_invstd, y, out)
+        ctx.save_for_backward(coarse, first_column(inds), skip, weights, gamma, save_mean, save_invstd, y, out)
         ctx.cfg = (bn_mode, act, biases is not None)
         return out
 
@@ -294,21 +279,13 @@ class _UpConv(Function):
         bn_mode, act, has_bias = ctx.cfg
         L = _lib.lib()
         (n1, c_up), (n2, c_skip), c_out = coarse.shape, skip.shape, weights.shape[1]
-        dev = coarse.device
         grad_out = grad_out.contiguous()
         need = ctx.needs_input_grad
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        gc = new(n1, c_up) if need[0] else None
-        gs = new(n2, c_skip) if need[2] else None
-        gw = new(c_up + c_skip, c_out) if need[3] else None
-        gb = new(c_out) if has_bias and need[4] else None
-        gg = new(c_out) if bn_mode and need[5] else None
-        gbeta = new(c_out) if bn_mode and need[6] else None
+        gc, gs, gw, gb, gg, gbeta = _wanted(_allocator(coarse.device), (need[0], (n1, c_up)), (need[2], (n2, c_skip)), (need[3], (c_up + c_skip, c_out)),
+                                            (has_bias and need[4], (c_out,)), (bn_mode and need[5], (c_out,)), (bn_mode and need[6], (c_out,)))
         grads = (gc, None, gs, gw, gb, gg, gbeta) + (None,) * 5
         if n2 == 0:
-            for g in (gc, gw, gb, gg, gbeta):
-                if g is not None:
-                    g.zero_()
+            _zeroed(gc, gw, gb, gg, gbeta)
             return grads
         order = inv_start = inv_src = None
         if gc is not None or gw is not None:
@@ -317,7 +294,7 @@ class _UpConv(Function):
             if tr is None:
                 raise NotImplementedError("up_conv: no transposed table for {} coarse rows (cbl_neighbor_transpose's limit)".format(n1))
             order, inv_start, inv_src = tr
-        ws = _up_workspace(L, n2, n1, c_up, c_skip, c_out, dev)
+        ws = _workspace(L.cbl_up_conv_workspace_bytes, coarse.device, _ll(n2), _ll(n1), _i(c_up), _i(c_skip), _i(c_out))
         _lib.check(L.cbl_up_conv_backward(_ll(n2), _ll(n1), _i(c_up), _i(c_skip), _i(c_out), _lib.ptr(coarse), _lib.ptr(inds0), _i(inds0.shape[1]), _lib.ptr(skip),
                                           _lib.ptr(weights), _i(bn_mode), _lib.ptr(gamma), _lib.ptr(save_mean), _lib.ptr(save_invstd), _i(act), _lib.ptr(y),
                                           _lib.ptr(out), _lib.ptr(grad_out), _lib.ptr(order), _lib.ptr(inv_start), _lib.ptr(inv_src), _lib.ptr(gc), _lib.ptr(gs),
@@ -336,9 +313,7 @@ def up_conv(coarse, upsample_inds, skip, weights, biases=None, gamma=None, beta=
     _chk(coarse, "coarse"); _chk(skip, "skip"); _chk(weights, "weights")
     if not (isinstance(upsample_inds, torch.Tensor) and upsample_inds.is_cuda and upsample_inds.dtype == torch.int32 and upsample_inds.is_contiguous()):
         raise TypeError("upsample_inds: expected a contiguous CUDA tensor of torch.int32")
-    for t, name in ((biases, "biases"), (gamma, "gamma"), (beta, "beta"), (moving_mean, "moving_mean"), (moving_variance, "moving_variance")):
-        if t is not None:
-            _chk(t, name)
+    _chk_optional(biases=biases, gamma=gamma, beta=beta, moving_mean=moving_mean, moving_variance=moving_variance)
     if coarse.dim() != 2 or skip.dim() != 2 or weights.dim() != 2 or upsample_inds.dim() != 2 or upsample_inds.shape[1] < 1:
         raise ValueError("up_conv: coarse (n1, c_up), upsample_inds (n2, max_num), skip (n2, c_skip) and weights (c_up + c_skip, c_out) expected")
     (n1, c_up), (n2, c_skip), (c_in, c_out) = coarse.shape, skip.shape, weights.shape
@@ -349,18 +324,7 @@ def up_conv(coarse, upsample_inds, skip, weights, biases=None, gamma=None, beta=
         raise NotImplementedError("up_conv: widths {} + {} -> {} (each at least 1, {} at most in and out)".format(c_up, c_skip, c_out, MAX_WIDTH))
     if n2 * upsample_inds.shape[1] >= 2 ** 31:
         raise NotImplementedError("up_conv: an upsample table of {} entries (fewer than 2^31)".format(n2 * upsample_inds.shape[1]))
-    if (gamma is None) != (beta is None):
-        raise ValueError("up_conv: gamma and beta come together (both None: bn=False)")
-    if gamma is None and (moving_mean is not None or moving_variance is not None):
-        raise ValueError("up_conv: moving statistics without a batch norm")
-    if (moving_mean is None) != (moving_variance is None):
-        raise ValueError("up_conv: moving_mean and moving_variance come together")
-    if gamma is not None and not is_training and moving_mean is None:
-        raise ValueError("up_conv: is_training=False needs moving_mean and moving_variance")
-    for t, name in ((biases, "biases"), (gamma, "gamma"), (beta, "beta"), (moving_mean, "moving_mean"), (moving_variance, "moving_variance")):
-        if t is not None and tuple(t.shape) != (c_out,):
-            raise ValueError("up_conv: {} of shape {}, ({},) expected".format(name, tuple(t.shape), c_out))
-    bn_mode = 0 if gamma is None else (1 if is_training else 2)
+    bn_mode = _bn_mode("up_conv", c_out, gamma, beta, moving_mean, moving_variance, is_training, biases)
     return _UpConv.apply(coarse, upsample_inds, skip, weights, biases, gamma, beta, (moving_mean, moving_variance), bn_mode, _ACTIVATIONS.get(activation_fn, 0),
                          float(bn_momentum), float(bn_eps))
 

@@ -88,6 +88,23 @@ def library(name, files, whole=()):
     return so
 
 
+def sanitizer_program(name, files, beside=False):
+    """-> path of the STAND-ALONE program oracle/_build/host/<name>_asan, rebuilt where stale: tests/host_emul/<name>_asan_main.cpp (its main; asan_common.h) and
+    the host translation units of `files` under -fsanitize=address,undefined.  The main includes its unit by name (found through -I), or — beside — the units
+    are compiled beside it.  Nothing of this is ever loaded into Python"""
+    main, exe = os.path.join(HERE, name + "_asan_main.cpp"), os.path.join(BUILD, name + "_asan")
+    tus = [translation_unit(f) for f in files]
+    if stale(exe, dependencies(files) + tus + [main, os.path.join(HERE, "asan_common.h")]):
+        subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-ffp-contract=off",
+                               "-Wno-unknown-pragmas"] + INCLUDES + (["-x", "c++", main] + tus if beside else ["-I" + BUILD, main]) + ["-o", exe])
+    return exe
+
+
+def run_sanitizer_program(exe):
+    """-> its subprocess.CompletedProcess (the emulator keeps its fibre stacks for the life of the process: no leak report)"""
+    return subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+
+
 @functools.lru_cache(maxsize=None)
 def _size_t_names():
     """the functions include/cbl_amd.h declares with a name ending in _bytes, read as contrastboundary_amd/_lib.py declared_symbols reads them"""

@@ -7,18 +7,14 @@ Python mirror leaves them to autograd.  The workspace is poisoned with 0xff and 
 A stand-alone AddressSanitizer program (tests/host_emul/adaptive_weight_mlp_asan_main.cpp) runs the same translation unit over the shape edges with heap
 buffers of exactly their logical size: an indexing error of a kernel surfaces there, on the CPU."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import adaptive_weight_general_oracle as G
 from tests import adaptive_weight_mlp_oracle as O
-from tests.host_emul.host_build import BUILD, HERE, INCLUDES, P, aligned, dependencies, load, nans, stale, translation_unit, transposed_table
+from tests.host_emul.host_build import P, aligned, load, nans, run_sanitizer_program, sanitizer_program, transposed_table
 
-ASAN_MAIN = os.path.join(HERE, "adaptive_weight_mlp_asan_main.cpp")
-ASAN_EXE = os.path.join(BUILD, "adaptive_weight_mlp_asan")
 cf = ctypes.c_float
 ACT = {"relu": 1, "leaky_relu": 2}
 # the grid caps and the most targets of a target-side trip (AWM_F_BLOCKS, AWM_BQ_BLOCKS, AWM_BT_BLOCKS of the kernel file, PAIR_TPT_MAX of pair_tile.h)
@@ -214,11 +210,6 @@ def test_unsupported_and_bad_arguments(host):
 def test_the_kernels_under_address_sanitizer():
     """the stand-alone program: the same translation unit with -fsanitize=address,undefined, forward + backward over the shape edges, heap buffers of exactly
     their logical size"""
-    tu = translation_unit("adaptive_weight_mlp")                        # the program's main includes it by name, from BUILD
-    if stale(ASAN_EXE, dependencies(["adaptive_weight_mlp"]) + [tu, ASAN_MAIN]):
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-ffp-contract=off",
-                               "-Wno-unknown-pragmas"] + INCLUDES + ["-I" + BUILD, ASAN_MAIN, "-o", ASAN_EXE])
-    # (the emulator keeps its fibre stacks for the life of the process: no leak report)
-    r = subprocess.run([ASAN_EXE], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    r = run_sanitizer_program(sanitizer_program("adaptive_weight_mlp", ["adaptive_weight_mlp"]))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "cases ok" in r.stdout

@@ -7,17 +7,13 @@ Python mirror leaves them to autograd.  The workspace is poisoned with 0xff and 
 A stand-alone AddressSanitizer program (tests/host_emul/pointwise_mlp_layers_asan_main.cpp) runs the same translation unit over the shape edges with heap
 buffers of exactly their logical size: an indexing error of a kernel surfaces there, on the CPU."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import pointwise_mlp_layers_oracle as O
-from tests.host_emul.host_build import BUILD, HERE, INCLUDES, P, aligned, dependencies, load, nans, stale, translation_unit, transposed_table
+from tests.host_emul.host_build import P, aligned, load, nans, run_sanitizer_program, sanitizer_program, transposed_table
 
-ASAN_MAIN = os.path.join(HERE, "pointwise_mlp_layers_asan_main.cpp")
-ASAN_EXE = os.path.join(BUILD, "pointwise_mlp_layers_asan")
 cf = ctypes.c_float
 
 
@@ -285,11 +281,6 @@ def test_the_mirror_refuses_what_the_kernels_do_not_cover():
 def test_the_kernels_under_address_sanitizer():
     """the stand-alone program: the same translation unit with -fsanitize=address,undefined, forward + backward over the shape edges, heap buffers of exactly
     their logical size"""
-    tu = translation_unit("pointwise_mlp_layers")                        # the program's main includes it by name, from BUILD
-    if stale(ASAN_EXE, dependencies(["pointwise_mlp_layers"]) + [tu, ASAN_MAIN]):
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-ffp-contract=off",
-                               "-Wno-unknown-pragmas"] + INCLUDES + ["-I" + BUILD, ASAN_MAIN, "-o", ASAN_EXE])
-    # (the emulator keeps its fibre stacks for the life of the process: no leak report)
-    r = subprocess.run([ASAN_EXE], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    r = run_sanitizer_program(sanitizer_program("pointwise_mlp_layers", ["pointwise_mlp_layers"]))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "cases ok" in r.stdout

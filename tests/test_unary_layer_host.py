@@ -5,17 +5,13 @@ Gradient cases with relu or leaky_relu assert, from the oracle, that no pre-acti
 A stand-alone AddressSanitizer program (tests/host_emul/unary_layer_asan_main.cpp) runs the same translation unit over the shape edges with heap buffers of
 exactly their documented size: an indexing error of a kernel surfaces there, on the CPU."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import unary_layer_oracle as O
-from tests.host_emul.host_build import BUILD, HERE, INCLUDES, P, aligned, dependencies, load, nans, stale, translation_unit
+from tests.host_emul.host_build import P, aligned, load, nans, run_sanitizer_program, sanitizer_program
 
-ASAN_MAIN = os.path.join(HERE, "unary_layer_asan_main.cpp")
-ASAN_EXE = os.path.join(BUILD, "unary_layer_asan")
 cf = ctypes.c_float
 ll = ctypes.c_longlong
 
@@ -211,11 +207,6 @@ def test_unsupported_and_bad_arguments(host):
 def test_the_kernels_under_address_sanitizer():
     """the stand-alone program: the same translation unit with -fsanitize=address,undefined, forward + backward over the shape edges, heap buffers of exactly
     their documented size"""
-    tu = translation_unit("unary_layer")                             # the program's main includes it by name, from BUILD
-    if stale(ASAN_EXE, dependencies(["unary_layer"]) + [tu, ASAN_MAIN]):
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-ffp-contract=off",
-                               "-Wno-unknown-pragmas"] + INCLUDES + ["-I" + BUILD, ASAN_MAIN, "-o", ASAN_EXE])
-    # (the emulator keeps its fibre stacks for the life of the process: no leak report)
-    r = subprocess.run([ASAN_EXE], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    r = run_sanitizer_program(sanitizer_program("unary_layer", ["unary_layer"]))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "cases ok" in r.stdout

@@ -5,18 +5,14 @@ call: an output that was accumulated into, or not written, stays NaN.  Gradient 
 pre-activation can flip between fp32 and float64.  A stand-alone AddressSanitizer program (tests/host_emul/up_conv_asan_main.cpp) runs the same translation
 units over the shape edges with heap buffers of exactly their documented size; nothing is loaded into Python under a sanitizer."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import up_conv_oracle as O
-from tests.host_emul.host_build import BUILD, HERE, INCLUDES, P, aligned, dependencies, load, nans, stale, translation_unit
+from tests.host_emul.host_build import P, aligned, load, nans, run_sanitizer_program, sanitizer_program
 
 FILES = ["up_conv", "neighbor_transpose"]                           # the entries, and cbl_grouping_backward_csr_rows (the segment sum)
-ASAN_MAIN = os.path.join(HERE, "up_conv_asan_main.cpp")
-ASAN_EXE = os.path.join(BUILD, "up_conv_asan")
 cf = ctypes.c_float
 ll = ctypes.c_longlong
 sz = ctypes.c_size_t
@@ -231,11 +227,6 @@ def test_unsupported_and_bad_arguments(host):
 def test_the_kernels_under_address_sanitizer():
     """the stand-alone program: the same translation units with -fsanitize=address,undefined, forward + backward over the shape edges, heap buffers of
     exactly their documented size"""
-    tus = [translation_unit(f) for f in FILES]
-    if stale(ASAN_EXE, dependencies(FILES) + tus + [ASAN_MAIN]):
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-ffp-contract=off",
-                               "-Wno-unknown-pragmas"] + INCLUDES + ["-x", "c++", ASAN_MAIN] + tus + ["-o", ASAN_EXE])
-    # (the emulator keeps its fibre stacks for the life of the process: no leak report)
-    r = subprocess.run([ASAN_EXE], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    r = run_sanitizer_program(sanitizer_program("up_conv", FILES, beside=True))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "cases ok" in r.stdout

@@ -25,7 +25,7 @@ import torch
 
 sys.path.insert(0, __file__.rsplit("/tools/", 1)[0])
 from contrastboundary_amd import convnet_path, local_aggregation, pointops, tf_ops, unary  # noqa: E402
-from contrastboundary_amd.local_aggregation import _first_column  # noqa: E402
+from contrastboundary_amd.local_aggregation import first_column  # noqa: E402
 
 FDIM = 72
 # (name, the finer layer, c_up, c_skip, c_out)
@@ -87,7 +87,7 @@ def main():
         fused = lambda: unary.up_conv(coarse, inds, skip, w, None, gamma, beta, mm, mv, **kw)
         composed = lambda: unary.conv1d_1x1(torch.cat([local_aggregation.nearest_upsample(coarse, inds), skip], 1), w, None, gamma, beta, mm, mv, **kw)
         # the transposed table both backward passes walk: built here, once, and found in the registry afterwards (as in a training loop)
-        assert pointops.neighbor_transpose(_first_column(inds), n1, build=True) is not None
+        assert pointops.neighbor_transpose(first_column(inds), n1, build=True) is not None
 
         def forward_only(fn):
             def run():
