@@ -995,6 +995,51 @@ size_t cbl_convnet_step_workspace_bytes(int nlayers, const CblConvnetLayer* laye
 int cbl_convnet_step(int nlayers, const CblConvnetLayer* layers, const long long* point_labels, int num_classes, float temperature, float weight,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The TF side's parameter update over FLAT fp32 buffers params / grads / accum of `total` elements cut into S segments, one segment per variable:
+ *   seg_begin (S+1) i64 on the device, strictly ascending (no empty segment), 0 <= seg_begin[0], seg_begin[S] <= total, any alignment (16-byte accesses
+ *   are used only where the three addresses allow them); seg_wd (S) f32 on the device, the variable's weight-decay coefficient, 0 = undecayed.
+ * The sweeps walk CHUNKS of at most 2048 elements that never cross a segment boundary.  cbl_tf_update_plan builds the chunk table once per layout ON THE
+ * HOST, from a host copy of seg_begin, into host memory (no device call: it validates the layout without a GPU); the caller uploads the plan_bytes bytes
+ * and hands the device copy, with *n_chunks, to the entries below.  The entries themselves do no host work beyond their launches and never synchronise.
+ *   plan (i32): chunk_of_segment (S+1) | segment_of_chunk (n_chunks);  n_chunks = sum of ceil(length / 2048) <= total / 2048 + S
+ * S == 0: every entry returns CBL_OK and touches nothing.  Results are deterministic (per-chunk fp64 partials, added per segment in a fixed order; no atomics).
+ * ---------------------------------------------------------------------------------------------- */
+size_t cbl_tf_update_plan_bytes(long long total, long long S);
+/* -> CBL_ERR_BAD_ARG for a null pointer, total < 0, S < 0, a seg_begin that descends, an empty segment, or a segment outside [0, total];
+ *    CBL_ERR_WORKSPACE for plan_bytes < cbl_tf_update_plan_bytes(total, S); CBL_ERR_UNSUPPORTED for more than 2^31 - 1 chunks */
+int cbl_tf_update_plan(long long total, long long S, const long long* seg_begin_host, void* plan_host, size_t plan_bytes, long long* n_chunks);
+size_t cbl_tf_update_workspace_bytes(long long total, long long S);
+
+/* The reference's weight loss  tensorflow/models/basic_operators.py:100-130 (_variable_with_weight_decay: wd * tf.nn.l2_loss(var)), :371-378, :444
+ * (tf_get_variable(..., wd=...)), local_aggregation_operators.py:720, summed by build_models.py:140-145 (l2_loss = tf.add_n(weight losses)):
+ *   loss[0] = sum_s seg_wd[s] * 1/2 sum_{i in s} params[i]^2;  seg_loss (S, may be NULL) receives the per-segment terms.
+ * Segments with seg_wd[s] == 0 are not read.  Workspace: cbl_tf_update_workspace_bytes(total, S). */
+int cbl_tf_weight_loss_forward(long long total, long long S, const float* params, const long long* seg_begin, const float* seg_wd,
+                               const int* plan, long long n_chunks, float* loss, float* seg_loss, void* workspace, size_t workspace_bytes, void* stream);
+/* its gradient (tf.gradients of the sum above):  grads[i] += grad_loss[0] * seg_wd[s] * params[i]  — the one ACCUMULATING entry: it adds to what the
+ * backward pass left in the flat gradient buffer.  Segments with seg_wd[s] == 0 are neither read nor written. */
+int cbl_tf_weight_loss_backward(long long total, long long S, const float* params, const long long* seg_begin, const float* seg_wd,
+                                const int* plan, long long n_chunks, const float* grad_loss, float* grads, void* stream);
+
+/* Per-variable clip + momentum step  tensorflow/utils/average_gradients.py:21-30 (tf.clip_by_norm(g, grad_norm) on every variable of a tower, before the
+ * towers are averaged) and tensorflow/utils/tf_graph_builder.py:99-100 (tf.train.MomentumOptimizer: accum = momentum * accum + g; var -= lr * accum).
+ *   mode & CBL_TF_UPDATE_CLIP:  h = g + (fold_decay ? seg_wd[s] * w : 0);  norm_s = sqrt(sum h^2) -> norms[s];
+ *                               g' = clip_norm > 0 ? (h * clip_norm) / max(norm_s, clip_norm) : h     (tf.clip_by_norm's own form; a zero gradient stays zero)
+ *   mode & CBL_TF_UPDATE_STEP:  a = momentum * a + grad_scale * g';  w -= lr[0] * a                  (lr is a DEVICE scalar: a replayed graph follows a schedule)
+ * CLIP alone writes g' into grads and leaves params / accum alone (accum may be NULL); STEP alone reads grads as they are (g' = g: fold_decay, clip_norm,
+ * seg_wd, norms and the workspace are not used and may be NULL); with both, grads is left holding g' and the update is the norm sweep plus ONE apply sweep.
+ * A data-parallel step is CLIP, all-reduce, STEP with grad_scale = 1 / world.
+ * seg_active (S, i32 on the device, may be NULL = all): segments with seg_active[s] == 0 are left alone by the apply sweep (a variable that received no
+ * gradient keeps its value and its momentum, as tf.train.Optimizer skips a variable whose gradient is None); their norm is still reported.
+ * Workspace (CLIP): cbl_tf_update_workspace_bytes(total, S). */
+#define CBL_TF_UPDATE_CLIP 1
+#define CBL_TF_UPDATE_STEP 2
+int cbl_tf_clip_update(long long total, long long S, int mode, int fold_decay, float* params, float* grads, float* accum,
+                       const long long* seg_begin, const float* seg_wd, const int* seg_active, const int* plan, long long n_chunks,
+                       float clip_norm, float momentum, float grad_scale, const float* lr, float* norms,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* N4  cpp_knn_batch_omp  tensorflow/ops/nearest_neighbors/knn_.cxx:104-135: dense batch (B,N,3) x (B,M,3) -> (B,M,K) int64 LOCAL indices.
  *     = cbl_knnquery on the flattened batch (offset = N, 2N, ...) followed by this conversion of the global int32 rows. */
 int cbl_knn_indices_to_local(int B, int M, int K, int N, const int* idx, long long* out, void* stream);
